@@ -19,7 +19,12 @@ Other SURVEY §8(d) workloads (measurement legs recorded under profiles/; not th
   --config 5   Presence: 100k Guid-keyed games x 8 players, 64k heartbeats per step, eager and hipGraph-replayed
   --config 6/7/8   directory mutation (f1), stream / reminder rings (f3), receive path (f2) legs
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..8]
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the result line; the CPU
+baseline legs (the oracle on the host cores, `cpu_baseline` on the line) run only with --full.  --dump-outputs DIR
+writes what the last timed step computed (route, act, order, offsets) as DIR/<name>.npy, so that two builds can be
+compared output for output (the inputs are seeded: the same arguments give the same messages).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..8] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 """
 from __future__ import annotations
@@ -148,7 +153,14 @@ def main():
     ap.add_argument("--host-io", choices=["pinned", "pageable", "narrow"], default=None,
                     help="config 2 at N=1: time the host-array P/Invoke call instead (orl_route_batch: 32-B headers in over "
                          "PCIe, route / act / order out; narrow = orl_route_batch_narrow: 8-B orl_wire8 records in, pinned)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline legs (the oracle on the host "
+                         "cores); off by default, so a plain run only sets up, warms up, times its steps and prints its line")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg all the same")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="configs 2/3 on one GPU: after the timed steps write the last step's outputs (route, act, order, "
+                         "offsets) as DIR/<name>.npy in float64: whole arrays up to DUMP_SAMPLE values, a fixed seeded "
+                         "sample of that many values of a larger one")
     ap.add_argument("--unregistered", type=float, default=0.0,
                     help="configs 2/3: fraction of the grains never registered (SURVEY §8(d) config 2's 10%% variant: "
                          "their messages miss the directory and are placed PreferLocal)")
@@ -171,6 +183,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         log(f"note: WORLD_SIZE={world} but --gpus={args.gpus}; using WORLD_SIZE")
+    if args.dump_outputs and (world != 1 or args.config not in (None, 2, 3) or args.host_io or args.local_ranks):
+        ap.error("--dump-outputs writes the device outputs of configs 2/3 on one GPU (no --host-io, no --local-ranks)")
 
     import torch
     import torch.distributed as dist
@@ -234,6 +248,24 @@ def timed_steps(args, torch, dist, world, step, sync):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     return elapsed, units
+
+
+DUMP_SAMPLE = 1 << 20  # values per dumped array: 4 arrays x 8 B x 2^20 = 32 MiB at the most
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(torch, out_dir, outputs):
+    """--dump-outputs: the arrays a caller of the timed path receives, as out_dir/<name>.npy in float64 (exact for the
+    u32 words).  An array of more than DUMP_SAMPLE values is sampled at DUMP_SAMPLE sorted positions drawn from a seeded
+    generator (the same positions for the same array length, run to run and build to build)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in outputs.items():
+        n = x.numel()
+        if n > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+            x = x[torch.from_numpy(pos).to(x.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), x.cpu().numpy().view(np.uint32).astype(np.float64))
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(outputs)}")
 
 
 def traffic_json_path(config):
@@ -436,8 +468,10 @@ def run_single_target(args, torch, dist, rank, world, local_rank):
         f"call {total_ms:.3f} ms over {nb} launches")
     traffic, traffic_src = (read_traffic(args.traffic_json or traffic_json_path(args.config), per_launch_msgs, world,
                                          args.config) if not args.unregistered else (None, None))
+    if args.dump_outputs:  # what the last timed step wrote (nothing has run on these buffers since)
+        dump_outputs(torch, args.dump_outputs, {"route": route, "act": act, "order": order, "offsets": offsets})
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         cpu = cpu_baseline(cl, n_grains, d_msgs, args.cpu_wall, zipf, 1.0 - args.unregistered)
     check = None
     if node is not None:  # correctness evidence of the multi-GPU run: every rank checks what it hosted (outside timing)
@@ -832,30 +866,31 @@ def run_chirper(args, torch):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     eng.close()
-    # CPU: the oracle's per-message path over the same step (1 thread, the reference's single silo)
-    o = cpu_ref.Oracle(1)
-    o.add_server(0, h0)
-    o.register(keys, np.arange(n_acc, dtype=np.uint32), np.zeros(n_acc, np.uint8))
-    reps = 0
-    t0 = time.perf_counter()
-    while True:
-        msgs, _ = cpu_ref.fanout_expand(off, ftgt, pubs, np.zeros(n_acc, np.uint8), tcd)
-        o.route_bucket_mt(msgs, n_acc, 1)
-        reps += 1
-        if time.perf_counter() - t0 > args.cpu_wall:
-            break
-    cpu_wall = time.perf_counter() - t0
-    log(f"config 1: {el * 1e6 / steps:.1f} us/step on the GPU (graph replay), {cpu_wall * 1e6 / reps:.1f} us/step on 1 CPU thread")
+    log(f"config 1: {el * 1e6 / steps:.1f} us/step on the GPU (graph replay)")
+    cpu = None
+    if args.full and not args.no_cpu:  # the oracle's per-message path over the same step (1 thread, the reference's single silo)
+        o = cpu_ref.Oracle(1)
+        o.add_server(0, h0)
+        o.register(keys, np.arange(n_acc, dtype=np.uint32), np.zeros(n_acc, np.uint8))
+        reps = 0
+        t0 = time.perf_counter()
+        while True:
+            msgs, _ = cpu_ref.fanout_expand(off, ftgt, pubs, np.zeros(n_acc, np.uint8), tcd)
+            o.route_bucket_mt(msgs, n_acc, 1)
+            reps += 1
+            if time.perf_counter() - t0 > args.cpu_wall:
+                break
+        cpu_wall = time.perf_counter() - t0
+        log(f"config 1: {cpu_wall * 1e6 / reps:.1f} us/step on 1 CPU thread")
+        cpu = {"value": n * reps / cpu_wall, "unit": "messages/s", "cores": 1, "kind": "port", "cpu_model": cpu_info()[0],
+               "sample": f"{reps} whole steps (expand + route + bucket, oracle/cpu_ref.cpp) on 1 thread"}
     return {"metric": "routed grain messages/sec (node)", "value": n * steps / el, "unit": "messages/s", "n_gpus": 1,
             "steps": steps, "warmup": args.warmup, "ms_per_step": el * 1e3 / steps, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u32/u64 integer",
             "data": "ChirperNetworkGenerator deterministic graph (ChirperNetworkGenerator.cs:306-345)",
             "config": {"workload": "config1: Chirper 1k accounts x 10 followers on one silo, every account publishes once "
                                    "(10k routed messages per step), fan-out + stages 1-4, hipGraph replay"},
-            "roofline": None,
-            "cpu_baseline": {"value": n * reps / cpu_wall, "unit": "messages/s", "cores": 1, "kind": "port",
-                             "cpu_model": cpu_info()[0],
-                             "sample": f"{reps} whole steps (expand + route + bucket, oracle/cpu_ref.cpp) on 1 thread"}}
+            "roofline": None, "cpu_baseline": cpu}
 
 
 # ---- config 4: CSR multicast fan-out ---------------------------------------------------------------------
@@ -912,7 +947,7 @@ def run_fanout(args, torch):
     per_step = emitted / args.steps
     bytes_launch = FANOUT_BYTES_PER_MSG * per_step + FANOUT_BYTES_PER_PUB * n_pub
     cpu = None
-    if not args.no_cpu:  # the oracle: the step's 1M publishes expanded (ref_fanout_expand) + stages 1-4, host cores
+    if args.full and not args.no_cpu:  # the oracle: the step's 1M publishes expanded (ref_fanout_expand) + stages 1-4, host cores
         from oracle import cpu_ref
         o = cpu_ref.Oracle(cl.n_silos)
         for s_ in range(cl.n_silos):
@@ -1257,7 +1292,7 @@ def run_wire(args, torch):
             traffic = rec.get("hbm_bytes_per_launch")
     eng.close()
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         cpu = wire_cpu_baseline(buf, offs, cl, args.cpu_wall)
     log("wire: " + ", ".join(f"{k} {v:.3f} ms" for k, v in out.items()) + f" per {n} frames (mean header {mean_hl:.0f} B)")
     ms = out["decode_route_stamp"]
@@ -1442,7 +1477,7 @@ def run_presence(args, torch):
     if eng2 is not eng:
         eng2.close()
     cpu = None
-    if not args.no_cpu:  # the oracle over the same step: game messages + the player fan-out named by the key table
+    if args.full and not args.no_cpu:  # the oracle over the same step: game messages + the player fan-out named by the key table
         from oracle import cpu_ref
         o = cpu_ref.Oracle(cl.n_silos)
         for s_ in range(cl.n_silos):

@@ -5,7 +5,7 @@
 #   TESTS="<pytest targets>"   GPU tests to run first (K=<-k expr> optional); empty: none
 #   AB="NAME=v1,v2;..."        bench A/B: one default-config bench line per value of each env var (BENCH_ARGS applies)
 #   BENCH_ARGS="..."           bench arguments (default --steps 20 --warmup 5 --no-cpu)
-#   CONFIGS="1 3 4 5"          extra bench lines, one per config (--config c --steps 10 --warmup 2)
+#   CONFIGS="1 3 4 5"          extra bench lines, one per config (--full --config c --steps 10 --warmup 2)
 #   PROF=1                     rocprofv3 kernel trace of the default bench (PROF_ARGS; stats to $OUT/trace)
 #   PMC="g1;g2"                extra rocprofv3 --pmc passes (one per ';'-separated group) over PROF_ARGS (PMC_ARGS: extra
 #                              rocprofv3 options, e.g. --kernel-include-regex k_probe_slice)
@@ -43,7 +43,7 @@ if [ -n "$AB" ]; then
 fi
 if [ -n "$CONFIGS" ]; then
   for c in $CONFIGS; do
-    timeout -k 10 400 python bench.py --config $c --steps 10 --warmup 2 ${CFG_ARGS} > $OUT/c$c.json 2> $OUT/c$c.log
+    timeout -k 10 400 python bench.py --full --config $c --steps 10 --warmup 2 ${CFG_ARGS} > $OUT/c$c.json 2> $OUT/c$c.log
     rc=$?; echo "config $c exit $rc: $(python3 -c "import json; d=json.load(open('$OUT/c$c.json')); print(d['ms_per_step'], 'ms', d['value'], d['unit'])" 2>/dev/null)"
     stop $rc
   done

@@ -94,7 +94,8 @@ def _id_hash_by_hand(text: str) -> int:
 
 
 @pytest.mark.parametrize("ep,gen", [("10.0.0.1:11111", 1), ("10.0.0.8:11111", 1), ("127.0.0.1:30000", -5),
-                                    ("[::1]:11111", 123456789)])
+                                    # explicit id: the generated one would hold "::", the separator of test ids
+                                    pytest.param("[::1]:11111", 123456789, id="ipv6-loopback:11111-123456789")])
 def test_g06_calc_id_hash_utf16le_bigendian(ep, gen):
     """SHA-256 over the UTF-16LE string Endpoint.ToString() + Generation.ToString(InvariantCulture) (a negative
     generation keeps its '-'), folded by XOR of 8 big-endian int32 words (hashlib here: a third SHA-256)."""
