@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function
 SRC = orleans_amd/csrc/route_kernels.hip orleans_amd/csrc/wire_codec.hip orleans_amd/csrc/orl_api.cpp orleans_amd/csrc/orl_node.cpp
-HDR = include/orleans_route.h orleans_amd/csrc/orl_internal.h
+HDR = include/orleans_route.h orleans_amd/csrc/orl_internal.h orleans_amd/csrc/part_lb_body.inc
 LIB = orleans_amd/liborleans_route.so
 OBJ = build/route_kernels.o build/wire_codec.o build/orl_api.o build/orl_node.o
 # RCCL (the node exchange); inside a torch process the soname resolves to torch's loaded copy

@@ -412,6 +412,58 @@ int orl_cache_add_or_update_device(orl_ctx* ctx, const orl_grain_key* d_keys, co
 int orl_cache_remove_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, uint8_t* d_removed, void* stream);
 int orl_cache_count(orl_ctx* ctx, uint64_t* n_out);
 
+/* ---- stateless-worker grains (StatelessWorkerDirector, src/OrleansRuntime/Placement/StatelessWorkerDirector.cs:35-80)
+ * A [StatelessWorker] grain is never registered in the grain directory (Catalog.cs:1156-1185, singleActivationMode =
+ * !activation.IsStatelessWorker): its messages need no ring owner, no partition probe and no cross-silo hop.  A
+ * context holds the stateless-worker types (TypeCodeData values with their MaxLocal: GrainTypeData.cs:43-50,115,
+ * StatelessWorkerPlacement.cs:44-49) and a local catalog: per (grain, silo) the silo's activations of the grain in
+ * insertion order (List<ActivationData>), each with a busy bit (busy = not (State == Valid && IsInactive), :54-55).
+ * A message whose header is not ORL_HDR_ADDRESS_COMPLETE and whose type is listed is routed from the catalog entry
+ * of (grain, sending silo); h = the uniform hash (aux with ORL_HDR_HASH_VALID), count = the entry's activations:
+ *   no entry (:46-47)                              NEW_PLACEMENT on the sending silo (OnAddActivation, :69-74)
+ *   an idle activation (:51-58)                    HIT, the first idle one in list order
+ *   all busy, count >= MaxLocal (:60-64)           HIT, act = list[count == 1 ? 0 : h % count] (h % count stands in for
+ *                                                  random.Next, as ORL_POLICY_HASH_SPREAD does for SafeRandom)
+ *   all busy, count < MaxLocal (:66)               NEW_PLACEMENT on the sending silo
+ * The route word: owner 0xFF (no CalculateTargetSilo), host = the sending silo, flags ORL_RF_STATELESS |
+ * ORL_RF_LOOPBACK (| ORL_RF_NEW_PLACEMENT).  The placement policy, the ring (an empty one and a stopping sender
+ * included), ORL_OPT_EXCLUDE_IF_STOPPING, the directory partition, the directory cache and functional[] play no part,
+ * and ORL_ST_OWNER_NULL is never produced for such a message.  A batch is addressed against the catalog as of its
+ * launch (host changes are uploaded before the next batch; orl_sw_set_busy_device runs in stream order).  The node's
+ * hop-1 partition keeps such messages on the sending rank.  Not covered: MaxLocal > 8, and the fan-out and KeyExt entry
+ * points below, which refuse to run while types are set rather than route such grains through the directory. */
+#define ORL_MAX_SW_TYPES 8u
+#define ORL_SW_MAX_LOCAL 8u
+#define ORL_RF_STATELESS 0x20u
+#define ORL_SW_ADDED 0u
+#define ORL_SW_DUPLICATE 1u    /* the list already holds MaxLocal: DuplicateActivationException (Catalog.cs:1176-1180) */
+#define ORL_SW_UNSUPPORTED 2u  /* type not listed, act >= n_act, silo out of range, or the handle is already in the list */
+/* The stateless-worker types: n <= ORL_MAX_SW_TYPES TypeCodeData values of category ORL_CAT_GRAIN, no duplicates,
+ * max_local[i] in 1..ORL_SW_MAX_LOCAL (else ORL_E_INVALID).  n = 0 turns the feature off.  Clears the catalog. */
+int orl_sw_types_set(orl_ctx* ctx, const uint64_t* type_code_data, const uint8_t* max_local, uint32_t n);
+/* Size the catalog for `capacity` (grain, silo) entries: next_pow2(2 * capacity) slots of 64 B.  Clears it. */
+int orl_sw_config(orl_ctx* ctx, uint64_t capacity);
+/* Catalog.RegisterMessageTarget for a stateless worker (Catalog.cs:1169-1181): host arrays, applied in array order;
+ * status[i] = ORL_SW_*.  ORL_E_CAPACITY, before anything changes, if the entries could pass half of the slots. */
+int orl_sw_add(orl_ctx* ctx, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n, uint8_t* status);
+/* Activation destroy (Catalog.UnregisterMessageTarget → List.Remove): the remaining activations keep their order; an
+ * emptied list frees its entry.  removed[i] = 1 when (key, silo) held the handle. */
+int orl_sw_remove(orl_ctx* ctx, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n,
+                  uint8_t* removed);
+/* ActivationData running / idle transitions: busy[i] != 0 marks the activation busy.  found[i] (optional) = 1 when
+ * (key, silo) holds the handle. */
+int orl_sw_set_busy(orl_ctx* ctx, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const uint8_t* busy,
+                    size_t n, uint8_t* found);
+/* The same over device arrays: one kernel on `stream`, no synchronisation.  An activation named twice in one batch
+ * must carry the same value.  d_found is optional.  The host mirror is re-read from the device on its next use. */
+int orl_sw_set_busy_device(orl_ctx* ctx, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                           const uint8_t* d_busy, size_t n, uint8_t* d_found, void* stream);
+/* The lists of (keys[i], silos[i]): count[i] activations in acts[i * ORL_SW_MAX_LOCAL ...] in list order, busy_mask[i]
+ * bit j = activation j is busy.  count 0: no entry. */
+int orl_sw_lookup_host(orl_ctx* ctx, const orl_grain_key* keys, const uint8_t* silos, size_t n, uint8_t* count,
+                       uint32_t* acts, uint8_t* busy_mask);
+int orl_sw_count(orl_ctx* ctx, uint64_t* n_entries);
+
 /* ---- outbound queues and client gateway buckets ------------------------------
  * Per routed message, the queue OutboundMessageQueue.SendMessage (src/OrleansRuntime/Messaging/
  * OutboundMessageQueue.cs:75-150) hands it to: ORL_OUTQ_REJECT when the route has no target (host) silo

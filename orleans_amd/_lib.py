@@ -50,6 +50,10 @@ OPT_TOTAL_GIVEN = 0x4
 SPLIT_REMOVE = 0x1
 RF_CACHED = 0x08
 RF_CACHE_STALE = 0x10
+RF_STATELESS = 0x20
+MAX_SW_TYPES = 8
+SW_MAX_LOCAL = 8
+SW_ADDED, SW_DUPLICATE, SW_UNSUPPORTED = 0, 1, 2
 RING_CONSISTENT, RING_VBUCKETS = 0, 1
 OUTQ_LOOPBACK, OUTQ_PING, OUTQ_SYSTEM, OUTQ_REJECT, OUTQ_OVERFLOW, OUTQ_UNKNOWN_SILO = (
     0xFFFFFFF0, 0xFFFFFFF1, 0xFFFFFFF2, 0xFFFFFFF3, 0xFFFFFFF4, 0xFFFFFFF5)
@@ -201,6 +205,14 @@ _SIGS = {
     "orl_cache_add_or_update_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
     "orl_cache_remove_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "orl_cache_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "orl_sw_types_set": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "orl_sw_config": (C.c_int, [_P, C.c_uint64]),
+    "orl_sw_add": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    "orl_sw_remove": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    "orl_sw_set_busy": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "orl_sw_set_busy_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "orl_sw_lookup_host": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "orl_sw_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "orl_sync": (C.c_int, [_P]),
     "orl_ctx_query": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64)]),
     "orl_bucket_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),

@@ -250,6 +250,20 @@ struct orl_ctx {
     uint64_t cache_slots = 0, cache_ub = 0, cache_tombs_ub = 0;
     uint64_t cache_cap = 0;       // LRU.MaximumSize (orl_cache_config's capacity)
     uint64_t cache_gen_free = 0;  // LRU.generationToFree: the generation of the last entry evicted
+    // stateless-worker grains (StatelessWorkerDirector.cs:35-80): the listed types with their MaxLocal, and the local
+    // catalog's host mirror (SwSlot), uploaded whole when the host changed it (sw_dirty).  orl_sw_set_busy_device makes
+    // the device table the newer one (sw_dev_newer): the host calls first read it back (sw_sync_host).  The two flags
+    // never hold together.
+    uint32_t sw_n = 0;
+    uint64_t sw_tcd[ORL_MAX_SW_TYPES] = {};
+    uint8_t sw_max[ORL_MAX_SW_TYPES] = {};
+    std::vector<SwSlot> sw_table;
+    uint64_t sw_mask = 0, sw_count = 0, sw_tombs = 0;
+    bool sw_dirty = false;
+    bool sw_dev_newer = false;
+    hipStream_t sw_dev_stream = nullptr;  // the stream of the last orl_sw_set_busy_device
+    SwSlot* d_sw = nullptr;
+    size_t d_sw_slots = 0;
     RouteParams hp{};
     RouteParams* d_params = nullptr;
     bool params_dirty = true;
@@ -543,7 +557,7 @@ int patch_dirty_slots(orl_ctx* c) {
 
 bool state_dirty(const orl_ctx* c) {
     return c->silo_hash_dirty || c->vr_dirty || c->silo_addr_dirty || c->gt_dirty || c->dir_dirty || c->params_dirty ||
-           !c->dirty_slots.empty();
+           !c->dirty_slots.empty() || c->sw_dirty;
 }
 
 int sync_device_state(orl_ctx* c) {
@@ -620,7 +634,31 @@ int sync_device_state(orl_ctx* c) {
         ORL_HIP(c, hipMemcpy(c->d_params, &c->hp, sizeof(RouteParams), hipMemcpyHostToDevice));
         c->params_dirty = false;
     }
+    if (c->sw_dirty) {  // the local catalog: small (64 B per slot), uploaded whole
+        if (c->d_sw_slots != c->sw_table.size()) {
+            if (c->d_sw) (void)hipFree(c->d_sw);
+            c->d_sw = nullptr;
+            c->d_sw_slots = 0;
+            if (!c->sw_table.empty()) {
+                ORL_HIP(c, hipMalloc((void**)&c->d_sw, c->sw_table.size() * sizeof(SwSlot)));
+                c->d_sw_slots = c->sw_table.size();
+            }
+        }
+        if (c->d_sw)
+            ORL_HIP(c, hipMemcpy(c->d_sw, c->sw_table.data(), c->sw_table.size() * sizeof(SwSlot), hipMemcpyHostToDevice));
+        c->sw_dirty = false;
+    }
     return ORL_OK;
+}
+
+// The SW kernel forms' argument: the listed types and the device catalog (n = 0: no types set, the plain forms run).
+SwView sw_view(const orl_ctx* c) {
+    SwView v{};
+    v.n = c->sw_n;
+    std::memcpy(v.tcd, c->sw_tcd, sizeof v.tcd);
+    v.table = c->d_sw;
+    v.mask = c->sw_mask;
+    return v;
 }
 
 DirView dir_view(const orl_ctx* c) {
@@ -720,7 +758,7 @@ int ensure_staging(orl_ctx* c, size_t in_bytes, size_t out_words) {
 
 void free_device(orl_ctx* c) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
-    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state);
+    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
     f(c->s.pairs_a); f(c->s.pairs_b); f(c->s.idx_a); f(c->s.sorted_keys); f(c->s.tile_hist); f(c->s.tile_cnt); f(c->s.scan_sums); f(c->s.digits); f(c->s.col_sums); f(c->s.col_tot); f(c->s.seg_hist); f(c->s.seg_carry); f(c->s.seg_meta); f(c->s.seg_lb); f(c->s.seg_lbctl); f(c->s.bstart); f(c->s.sstart); f(c->s.gap_q); f(c->s.hot); f(c->s.hot_rows); f(c->s.hot_bmax); f(c->s.pick_word); f(c->s.fan_blk); f(c->s.lsd_hot);
     for (auto& L : c->s.lb) {
         f(L.state);
@@ -1420,8 +1458,9 @@ int route_impl(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, u
     if ((r = prepare_probe(c, st))) return r;
     if (ev) ORL_HIP(c, hipEventRecord(ev[0], st));
     if (fmt == 8 && c->hp.n_wire_types == 0) return fail(c, ORL_E_STATE, "8-byte records need the wire types (orl_wire_types_set)");
+    const SwView swv = sw_view(c);  // stateless-worker types set: the SW kernel forms (the plain ones otherwise, as before)
     int e = launch_route_bucket(c->d_params, dir_view(c), d_in, fmt, n, opts, c->cfg.n_act, d_route, d_act, d_order,
-                                d_off, c->s, st, ev ? ev[1] : nullptr, ev ? ev[2] : nullptr, d_in_act);
+                                d_off, c->s, st, ev ? ev[1] : nullptr, ev ? ev[2] : nullptr, d_in_act, swv.n ? &swv : nullptr);
     if (!e && ctx_cache_on(c)) e = launch_cache_gen_advance(c->d_cache, c->cache_slots - 1, n, st);  // the lookups' LRU stamps
     if (e) return hipfail(c, (hipError_t)e, "route launch");
     if (ev) ORL_HIP(c, hipEventRecord(ev[3], st));
@@ -1437,6 +1476,8 @@ int ctx_route_received(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t
 }
 
 bool ctx_cache_on(orl_ctx* c) { return c && c->d_cache && c->hp.cache_on; }
+
+bool ctx_sw_on(const orl_ctx* c) { return c && c->sw_n != 0; }
 
 int ctx_keyext_prepare(orl_ctx* c) { return upload_keyext(c); }
 
@@ -1475,6 +1516,8 @@ int orl_route_keyext_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint3
                             const uint8_t* d_blob, uint64_t blob_bytes, uint32_t* d_route, uint32_t* d_act, uint32_t* d_order,
                             uint32_t* d_off, void* stream) {
     if (!c) return ORL_E_INVALID;
+    if (c->sw_n)  // no stateless-worker form of the KeyExt route: refuse rather than route such grains by the directory
+        return fail(c, ORL_E_STATE, "the KeyExt route does not take stateless-worker types (orl_sw_types_set)");
     if (n && (!d_ext || !d_blob)) return fail(c, ORL_E_INVALID, "null KeyExt references or blob");
     const bool buckets = !(opts & ORL_OPT_NO_BUCKETS);
     if (buckets && (!d_off || (n && !d_order))) return fail(c, ORL_E_INVALID, "null order/offsets buffer");
@@ -1566,6 +1609,16 @@ int fanout_impl(orl_ctx* c, const orl_msg_hdr* d_direct, size_t n_direct, const 
                 uint64_t follower_tcd, uint32_t opts, uint64_t* d_pub_offsets, uint32_t* d_route, uint32_t* d_act,
                 uint32_t* d_order, uint32_t* d_off, uint64_t* n_out, void* stream) {
     if (!c || !n_out) return ORL_E_INVALID;
+    // k_fanout_route has no stateless-worker form.  The follower-type form can tell from its one type that no emitted
+    // message is of a listed type; the key-table and mixed forms cannot, and refuse while types are set (expand + route
+    // is the supported way: orl_fanout_expand_device, then a route entry).
+    if (c->sw_n && (d_keys || n_direct || d_direct))
+        return fail(c, ORL_E_STATE, "the key-table and mixed fan-out forms do not take stateless-worker types (orl_sw_types_set): "
+                                    "expand (orl_fanout_expand_device), then route");
+    for (uint32_t i = 0; i < c->sw_n; ++i)
+        if (c->sw_tcd[i] == follower_tcd)
+            return fail(c, ORL_E_INVALID, "follower type %016llx is a stateless-worker type: expand (orl_fanout_expand_device), "
+                                          "then route", (unsigned long long)follower_tcd);
     if (!d_csr_off || !d_csr_tgt || !d_pub_offsets || !d_route || !d_act) return fail(c, ORL_E_INVALID, "null device buffer");
     if (n_pub && (!d_pubs || !d_pub_silo)) return fail(c, ORL_E_INVALID, "null publisher buffer");
     if (n_direct && !d_direct) return fail(c, ORL_E_INVALID, "null direct message buffer");
@@ -1614,6 +1667,9 @@ int orl_fanout_route_keys_device(orl_ctx* c, const uint64_t* d_csr_off, const ui
                                  const orl_grain_key* d_keys, const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub,
                                  uint32_t opts, uint64_t* d_pub_offsets, uint32_t* d_route, uint32_t* d_act, uint32_t* d_order,
                                  uint32_t* d_off, uint64_t* n_out, void* stream) {
+    if (c && c->sw_n)
+        return fail(c, ORL_E_STATE, "the key-table fan-out form does not take stateless-worker types (orl_sw_types_set): "
+                                    "expand (orl_fanout_expand_device), then route");
     if (c && !d_keys) return fail(c, ORL_E_INVALID, "null follower key table");
     return fanout_impl(c, nullptr, 0, d_csr_off, d_csr_tgt, d_keys, d_pubs, d_pub_silo, n_pub, 0, opts, d_pub_offsets, d_route,
                        d_act, d_order, d_off, n_out, stream);
@@ -1624,6 +1680,9 @@ int orl_fanout_route_mixed_device(orl_ctx* c, const orl_msg_hdr* d_direct, size_
                                   const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub, uint32_t opts,
                                   uint64_t* d_pub_offsets, uint32_t* d_route, uint32_t* d_act, uint32_t* d_order,
                                   uint32_t* d_off, uint64_t* n_out, void* stream) {
+    if (c && c->sw_n)
+        return fail(c, ORL_E_STATE, "the mixed fan-out form does not take stateless-worker types (orl_sw_types_set): "
+                                    "expand (orl_fanout_expand_device), then route");
     return fanout_impl(c, d_direct, n_direct, d_csr_off, d_csr_tgt, d_keys, d_pubs, d_pub_silo, n_pub, d_keys ? 0 : follower_tcd,
                        opts, d_pub_offsets, d_route, d_act, d_order, d_off, n_out, stream);
 }
@@ -1681,8 +1740,9 @@ int orl_partition_by_owner_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n,
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
+    const SwView swv = sw_view(c);
     int e = launch_partition_by_owner(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, d_out, d_src, d_counts,
-                                      c->s, st);
+                                      c->s, st, swv.n ? &swv : nullptr);
     if (e) return hipfail(c, (hipError_t)e, "partition launch");
     return ORL_OK;
 }
@@ -1695,8 +1755,9 @@ int orl_partition_by_owner_padded_device(orl_ctx* c, const orl_msg_hdr* d_in, si
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
+    const SwView swv = sw_view(c);
     int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, 32, d_src,
-                                    d_counts, nullptr, c->s, st);
+                                    d_counts, nullptr, c->s, st, nullptr, 0, nullptr, nullptr, swv.n ? &swv : nullptr);
     if (e) return hipfail(c, (hipError_t)e, "padded partition launch");
     return ORL_OK;
 }
@@ -1715,9 +1776,10 @@ int ctx_partition_padded(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
     const bool cached = d_act_out && ctx_cache_on(c);
+    const SwView swv = sw_view(c);
     int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, fmt, nullptr,
                                     d_counts, d_status, c->s, st, cached ? c->d_cache : nullptr,
-                                    cached ? c->cache_slots - 1 : 0, cached ? d_act_out : nullptr, kxl);
+                                    cached ? c->cache_slots - 1 : 0, cached ? d_act_out : nullptr, kxl, swv.n ? &swv : nullptr);
     if (!e && cached) e = launch_cache_gen_advance(c->d_cache, c->cache_slots - 1, n, st);  // the sender's lookups' LRU stamps
     if (e) return hipfail(c, (hipError_t)e, "node partition launch");
     return ORL_OK;
@@ -1734,8 +1796,9 @@ int orl_partition_compact_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, 
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
+    const SwView swv = sw_view(c);
     int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, 16, d_src,
-                                    d_counts, d_status, c->s, st);
+                                    d_counts, d_status, c->s, st, nullptr, 0, nullptr, nullptr, swv.n ? &swv : nullptr);
     if (e) return hipfail(c, (hipError_t)e, "compact partition launch");
     return ORL_OK;
 }
@@ -1750,8 +1813,9 @@ int orl_partition_narrow_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, u
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
+    const SwView swv = sw_view(c);
     int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, 8, d_src,
-                                    d_counts, d_status, c->s, st);
+                                    d_counts, d_status, c->s, st, nullptr, 0, nullptr, nullptr, swv.n ? &swv : nullptr);
     if (e) return hipfail(c, (hipError_t)e, "narrow partition launch");
     return ORL_OK;
 }
@@ -2204,6 +2268,246 @@ int orl_client_buckets_device(orl_ctx* c, const orl_msg_hdr* d_msgs, size_t n, u
     if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
     int e = launch_client_buckets(d_msgs, n, n_buckets, d_bucket, stream ? stream : c->stream);
     if (e) return hipfail(c, (hipError_t)e, "client buckets launch");
+    return ORL_OK;
+}
+
+}  // extern "C"
+
+// ---- stateless-worker grains: the local catalog's host mirror -----------------------------------------
+namespace {
+
+// The mirror after orl_sw_set_busy_device: wait for that stream, then read the table back (only busy bits can differ).
+int sw_sync_host(orl_ctx* c) {
+    if (!c->sw_dev_newer) return ORL_OK;
+    ORL_HIP(c, hipSetDevice(c->cfg.device));
+    ORL_HIP(c, hipStreamSynchronize(c->sw_dev_stream));
+    if (c->d_sw && c->d_sw_slots == c->sw_table.size())
+        ORL_HIP(c, hipMemcpy(c->sw_table.data(), c->d_sw, c->sw_table.size() * sizeof(SwSlot), hipMemcpyDeviceToHost));
+    c->sw_dev_newer = false;
+    return ORL_OK;
+}
+
+void sw_clear(orl_ctx* c, uint64_t slots) {
+    c->sw_table.assign(slots, SwSlot{});
+    c->sw_mask = slots ? slots - 1 : 0;
+    c->sw_count = c->sw_tombs = 0;
+    c->sw_dirty = true;
+    c->sw_dev_newer = false;
+}
+
+int sw_type_index(const orl_ctx* c, uint64_t tcd) {
+    for (uint32_t i = 0; i < c->sw_n; ++i)
+        if (c->sw_tcd[i] == tcd) return (int)i;
+    return -1;
+}
+
+// Slot of (key, silo) in the mirror, or -1; *free_slot = the first reusable slot (tombstone or chain end) of the chain.
+int64_t sw_find(const orl_ctx* c, const orl_grain_key& k, uint32_t silo, int64_t* free_slot) {
+    int64_t fr = -1;
+    if (!c->sw_table.empty()) {
+        uint64_t i = sw_start(jenkins3(k.type_code_data, k.n0, k.n1), silo, c->sw_mask);
+        for (uint64_t step = 0; step <= c->sw_mask; ++step) {
+            const SwSlot& s = c->sw_table[i];
+            if (s.state == SLOT_EMPTY) { if (fr < 0) fr = (int64_t)i; break; }
+            if (s.state == SLOT_TOMB) { if (fr < 0) fr = (int64_t)i; }
+            else if (s.silo == silo && s.tcd == k.type_code_data && s.n0 == k.n0 && s.n1 == k.n1) {
+                if (free_slot) *free_slot = fr;
+                return (int64_t)i;
+            }
+            i = (i + 1) & c->sw_mask;
+        }
+    }
+    if (free_slot) *free_slot = fr;
+    return -1;
+}
+
+int sw_pos(const SwSlot& s, uint32_t act) {
+    for (uint32_t p = 0; p < s.count; ++p)
+        if (s.act[p] == act) return (int)p;
+    return -1;
+}
+
+// Rebuild the mirror without tombstones (same slot count).
+void sw_rehash(orl_ctx* c) {
+    std::vector<SwSlot> old;
+    old.swap(c->sw_table);
+    c->sw_table.assign(old.size(), SwSlot{});
+    c->sw_tombs = 0;
+    for (const SwSlot& s : old) {
+        if (s.state != SLOT_FULL) continue;
+        uint64_t i = sw_start(jenkins3(s.tcd, s.n0, s.n1), s.silo, c->sw_mask);
+        while (c->sw_table[i].state != SLOT_EMPTY) i = (i + 1) & c->sw_mask;
+        c->sw_table[i] = s;
+    }
+    c->sw_dirty = true;
+}
+
+bool sw_item_ok(const orl_ctx* c, const orl_grain_key& k, uint32_t act, uint32_t silo) {
+    return sw_type_index(c, k.type_code_data) >= 0 && act < c->cfg.n_act && silo < c->n_silos;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orl_sw_types_set(orl_ctx* c, const uint64_t* tcd, const uint8_t* max_local, uint32_t n) {
+    if (!c) return ORL_E_INVALID;
+    if (n > ORL_MAX_SW_TYPES) return fail(c, ORL_E_INVALID, "stateless-worker types: n = %u (at most %u)", n, ORL_MAX_SW_TYPES);
+    if (n && (!tcd || !max_local)) return fail(c, ORL_E_INVALID, "null type or MaxLocal array");
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((uint32_t)(tcd[i] >> 56) != ORL_CAT_GRAIN)  // GrainTypeData describes grain classes (GrainTypeData.cs:43-50)
+            return fail(c, ORL_E_INVALID, "stateless-worker type %u: category %u is not ORL_CAT_GRAIN", i, (uint32_t)(tcd[i] >> 56));
+        if (max_local[i] < 1 || max_local[i] > ORL_SW_MAX_LOCAL)
+            return fail(c, ORL_E_INVALID, "stateless-worker type %u: MaxLocal %u outside 1..%u", i, max_local[i], ORL_SW_MAX_LOCAL);
+        for (uint32_t j = 0; j < i; ++j)
+            if (tcd[i] == tcd[j]) return fail(c, ORL_E_INVALID, "stateless-worker types: entry %u repeats entry %u", i, j);
+    }
+    c->sw_n = n;
+    std::memset(c->sw_tcd, 0, sizeof c->sw_tcd);
+    std::memset(c->sw_max, 0, sizeof c->sw_max);
+    for (uint32_t i = 0; i < n; ++i) {
+        c->sw_tcd[i] = tcd[i];
+        c->sw_max[i] = max_local[i];
+    }
+    // the lists were kept under the old types' MaxLocal: start over (a first set sizes the catalog for 1024 entries)
+    sw_clear(c, n && c->sw_table.empty() ? next_pow2(2 * 1024) : c->sw_table.size());
+    return ORL_OK;
+}
+
+int orl_sw_config(orl_ctx* c, uint64_t capacity) {
+    if (!c) return ORL_E_INVALID;
+    if (capacity > (1ull << 30)) return fail(c, ORL_E_INVALID, "catalog capacity %llu too large", (unsigned long long)capacity);
+    sw_clear(c, next_pow2(2 * std::max<uint64_t>(capacity, 1)));
+    return ORL_OK;
+}
+
+int orl_sw_add(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n, uint8_t* status) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!keys || !acts || !silos || !status)) return fail(c, ORL_E_INVALID, "null array");
+    if (int r = sw_sync_host(c)) return r;
+    // entries this batch can create: the distinct (grain, silo) pairs of supported items that have no entry yet
+    std::vector<std::pair<orl_grain_key, uint32_t>> fresh;
+    for (size_t i = 0; i < n; ++i) {
+        if (!sw_item_ok(c, keys[i], acts[i], silos[i]) || sw_find(c, keys[i], silos[i], nullptr) >= 0) continue;
+        bool seen = false;
+        for (const auto& f : fresh)
+            seen = seen || (f.second == silos[i] && f.first.type_code_data == keys[i].type_code_data && f.first.n0 == keys[i].n0 &&
+                            f.first.n1 == keys[i].n1);
+        if (!seen) fresh.push_back({keys[i], silos[i]});
+        if (fresh.size() > c->sw_table.size()) break;  // already past any capacity
+    }
+    if ((c->sw_count + fresh.size()) * 2 > c->sw_table.size())
+        return fail(c, ORL_E_CAPACITY, "stateless-worker catalog full: %llu + %zu entries, %zu slots (orl_sw_config)",
+                    (unsigned long long)c->sw_count, fresh.size(), c->sw_table.size());
+    if ((c->sw_count + c->sw_tombs + fresh.size()) * 2 > c->sw_table.size()) sw_rehash(c);
+    for (size_t i = 0; i < n; ++i) {
+        const int t = sw_type_index(c, keys[i].type_code_data);
+        if (!sw_item_ok(c, keys[i], acts[i], silos[i])) { status[i] = ORL_SW_UNSUPPORTED; continue; }
+        int64_t fr = -1;
+        const int64_t at = sw_find(c, keys[i], silos[i], &fr);
+        if (at >= 0) {
+            SwSlot& s = c->sw_table[at];
+            if (sw_pos(s, acts[i]) >= 0) { status[i] = ORL_SW_UNSUPPORTED; continue; }
+            if (s.count >= s.max_local) { status[i] = ORL_SW_DUPLICATE; continue; }  // Catalog.cs:1176-1180
+            s.act[s.count++] = acts[i];  // appended, idle (its busy bit is clear: removal keeps the bits above count zero)
+        } else {
+            SwSlot& s = c->sw_table[fr];
+            if (s.state == SLOT_TOMB) --c->sw_tombs;
+            s = SwSlot{};
+            s.tcd = keys[i].type_code_data; s.n0 = keys[i].n0; s.n1 = keys[i].n1;
+            s.silo = silos[i];
+            s.count = 1;
+            s.state = SLOT_FULL;
+            s.max_local = c->sw_max[t];
+            s.act[0] = acts[i];
+            ++c->sw_count;
+        }
+        status[i] = ORL_SW_ADDED;
+        c->sw_dirty = true;
+    }
+    return ORL_OK;
+}
+
+int orl_sw_remove(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n, uint8_t* removed) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!keys || !acts || !silos)) return fail(c, ORL_E_INVALID, "null array");
+    if (int r = sw_sync_host(c)) return r;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
+        const int p = at >= 0 ? sw_pos(c->sw_table[at], acts[i]) : -1;
+        if (removed) removed[i] = p >= 0 ? 1 : 0;
+        if (p < 0) continue;
+        SwSlot& s = c->sw_table[at];
+        for (uint32_t q = (uint32_t)p; q + 1 < s.count; ++q) s.act[q] = s.act[q + 1];  // List.Remove: the order stays
+        s.act[--s.count] = 0;
+        s.busy = (uint8_t)((s.busy & ((1u << p) - 1u)) | ((s.busy >> (p + 1)) << p));
+        if (s.count == 0) {  // an emptied list frees its entry
+            s = SwSlot{};
+            s.state = SLOT_TOMB;
+            --c->sw_count;
+            ++c->sw_tombs;
+        }
+        c->sw_dirty = true;
+    }
+    return ORL_OK;
+}
+
+int orl_sw_set_busy(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const uint8_t* busy,
+                    size_t n, uint8_t* found) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!keys || !acts || !silos || !busy)) return fail(c, ORL_E_INVALID, "null array");
+    if (int r = sw_sync_host(c)) return r;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
+        const int p = at >= 0 ? sw_pos(c->sw_table[at], acts[i]) : -1;
+        if (found) found[i] = p >= 0 ? 1 : 0;
+        if (p < 0) continue;
+        SwSlot& s = c->sw_table[at];
+        const uint8_t b = busy[i] ? (uint8_t)(s.busy | (1u << p)) : (uint8_t)(s.busy & ~(1u << p));
+        if (b != s.busy) {
+            s.busy = b;
+            c->sw_dirty = true;
+        }
+    }
+    return ORL_OK;
+}
+
+int orl_sw_set_busy_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                           const uint8_t* d_busy, size_t n, uint8_t* d_found, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!d_keys || !d_acts || !d_silos || !d_busy)) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
+    if (c->sw_n == 0) return fail(c, ORL_E_STATE, "no stateless-worker types set (orl_sw_types_set)");
+    if (int r = sync_device_state(c)) return r;  // host changes first (refuses a host-only context)
+    if (!c->d_sw) return fail(c, ORL_E_STATE, "no stateless-worker catalog on the device");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_sw_set_busy(c->d_sw, c->sw_mask, d_keys, d_acts, d_silos, d_busy, n, d_found, st);
+    if (e) return hipfail(c, (hipError_t)e, "busy-bit launch");
+    if (n) {
+        c->sw_dev_newer = true;
+        c->sw_dev_stream = st;
+    }
+    return ORL_OK;
+}
+
+int orl_sw_lookup_host(orl_ctx* c, const orl_grain_key* keys, const uint8_t* silos, size_t n, uint8_t* count, uint32_t* acts,
+                       uint8_t* busy_mask) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!keys || !silos || !count || !acts || !busy_mask)) return fail(c, ORL_E_INVALID, "null array");
+    if (int r = sw_sync_host(c)) return r;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
+        count[i] = at >= 0 ? c->sw_table[at].count : 0;
+        busy_mask[i] = at >= 0 ? c->sw_table[at].busy : 0;
+        for (uint32_t p = 0; p < ORL_SW_MAX_LOCAL; ++p)
+            acts[i * ORL_SW_MAX_LOCAL + p] = (at >= 0 && p < c->sw_table[at].count) ? c->sw_table[at].act[p] : ORL_NO_ACT;
+    }
+    return ORL_OK;
+}
+
+int orl_sw_count(orl_ctx* c, uint64_t* n) {
+    if (!c || !n) return ORL_E_INVALID;
+    *n = c->sw_count;
     return ORL_OK;
 }
 

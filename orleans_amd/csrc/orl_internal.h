@@ -71,6 +71,33 @@ __host__ __device__ inline uint64_t dir_slot(uint32_t h, uint64_t mask) {
     return ((uint64_t)fmix32(h) * (mask + 1)) >> 32;
 }
 
+// ---- stateless-worker local catalog (StatelessWorkerDirector.cs:35-80, Catalog.cs:1156-1185) -------
+// One 64-B slot (one cache line, one read per message) per (grain, silo): the silo's activations of the grain in
+// insertion order (List<ActivationData>) with a busy bit each.  Open addressing from sw_start(), linear probing, load
+// <= 0.5, tombstones as in DirSlot.  max_local is the grain type's MaxLocal, copied in at add time so the route
+// kernel needs no second table.
+struct alignas(64) SwSlot {
+    uint64_t tcd, n0, n1;
+    uint8_t silo;
+    uint8_t count;      // activations in act[0, count)
+    uint8_t busy;       // bit i: act[i] is busy (not (State == Valid && IsInactive), StatelessWorkerDirector.cs:54-55)
+    uint8_t state;      // SLOT_EMPTY / SLOT_FULL / SLOT_TOMB
+    uint8_t max_local;
+    uint8_t pad[3];
+    uint32_t act[ORL_SW_MAX_LOCAL];
+};
+static_assert(sizeof(SwSlot) == 64, "catalog slot must be one 64-B line");
+
+// What the SW kernel instantiations get beside RouteParams (by value, as a kernel argument): the listed types and the
+// device catalog.  n == 0: the feature is off (no SW kernel is launched).
+struct SwView {
+    uint64_t tcd[ORL_MAX_SW_TYPES];
+    const SwSlot* table;
+    uint64_t mask;
+    uint32_t n;
+    uint32_t pad;
+};
+
 // ---- Jenkins lookup2, 24-byte form (JenkinsHash.cs:54-65, 126-144) ---------------------------------
 #define ORL_MIX(a, b, c)                 \
     do {                                 \
@@ -98,6 +125,11 @@ __host__ __device__ inline uint32_t jenkins3(uint64_t u1, uint64_t u2, uint64_t 
     c += 24u;
     ORL_MIX(a, b, c);
     return c;
+}
+
+// Start slot of (grain, silo) in a catalog of mask + 1 slots; h = the grain's uniform hash.
+__host__ __device__ inline uint64_t sw_start(uint32_t h, uint32_t silo, uint64_t mask) {
+    return dir_slot(h ^ (silo * 0x9E3779B9u), mask);
 }
 
 // ---- f2: SiloAddress -> silo index (wire decoder) ----------------------------------------------------
@@ -337,7 +369,8 @@ int launch_probe_build(const DirSlot* d_dir, uint64_t slots, const RouteParams* 
 int launch_route_bucket(const RouteParams* d_params, const DirView& dv,
                         const void* d_in, int fmt, size_t n, uint32_t opts, uint32_t n_act, uint32_t* d_route,
                         uint32_t* d_act, uint32_t* d_order, uint32_t* d_offsets, const Scratch& s, void* stream,
-                        void* ev_route_begin, void* ev_route_end, const uint32_t* d_in_act = nullptr);
+                        void* ev_route_begin, void* ev_route_end, const uint32_t* d_in_act = nullptr,
+                        const SwView* sw = nullptr);
 int launch_fanout_route_bucket(const RouteParams* d_params, const DirView& dv, const orl_msg_hdr* d_direct, size_t n_direct,
                                const uint64_t* d_csr_off, const uint32_t* d_csr_tgt, const orl_grain_key* d_follower_keys,
                                const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub, uint64_t follower_tcd,
@@ -409,7 +442,10 @@ int launch_partition_padded(const RouteParams* d_params, const orl_msg_hdr* d_in
                             const uint8_t* d_rank_of_silo, uint32_t nranks, uint32_t my_rank, uint64_t stride,
                             void* d_out, int fmt, uint32_t* d_src_index, uint64_t* d_counts, uint32_t* d_wire_status,
                             Scratch& s, void* stream, const DirSlot* d_cache = nullptr, uint64_t cmask = 0,
-                            uint32_t* d_act_out = nullptr, const KxLanes* kxl = nullptr);
+                            uint32_t* d_act_out = nullptr, const KxLanes* kxl = nullptr, const SwView* sw = nullptr);
+// The busy bits of catalog activations (orl_sw_set_busy_device): d_found[i] = 1 when (key, silo) holds act i.
+int launch_sw_set_busy(SwSlot* d_table, uint64_t mask, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                       const uint8_t* d_silos, const uint8_t* d_busy, size_t n, uint8_t* d_found, void* stream);
 // The received ext-ref lane of a chunk: source s's references (cnt[s] records, in rank order) += base[s].
 int launch_ext_rebase(orl_ext_ref* d_refs, uint64_t n, uint32_t nranks, const uint64_t* cnt, const uint64_t* base, void* stream);
 // Stage 4 alone over already-routed messages (activation handles): histogram + bucket_after_route.
@@ -446,6 +482,9 @@ int ctx_route_keyext_received(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uin
 int ctx_keyext_prepare(orl_ctx* c);
 // Whether the context's directory cache is configured and holds entries (the partition's cached destinations).
 bool ctx_cache_on(orl_ctx* c);
+// Whether the context has stateless-worker types set (orl_sw_types_set): ctx_partition_padded and ctx_route_received
+// then launch the SW kernel forms on their own.
+bool ctx_sw_on(const orl_ctx* c);
 // Device address of the context's stage-4 look-back error word (Scratch::s4_err).
 const uint32_t* ctx_stage4_err(const orl_ctx* c);
 // Stages 1-3 of received exchange records (fmt 8 / 16 / 32, no stage 4) with an optional act lane d_in_act: records the
@@ -466,6 +505,7 @@ int launch_keyext_route(const RouteParams* d_params, const orl_msg_hdr* d_in, si
                         const uint8_t* d_tblob, uint32_t excl, uint32_t* d_route, uint32_t* d_act, void* stream);
 int launch_partition_by_owner(const RouteParams* d_params, const orl_msg_hdr* d_in, size_t n, uint32_t opts,
                               const uint8_t* d_rank_of_silo, uint32_t nranks, uint32_t my_rank, orl_msg_hdr* d_out,
-                              uint32_t* d_src_index, uint64_t* d_counts, const Scratch& s, void* stream);
+                              uint32_t* d_src_index, uint64_t* d_counts, const Scratch& s, void* stream,
+                              const SwView* sw = nullptr);
 
 }  // namespace orl

@@ -1036,6 +1036,8 @@ int orl_node_route_batch_keyext_device(orl_node* nd, const orl_msg_hdr* d_in, si
     if (!nd || !res) return ORL_E_INVALID;
     if (n && (!d_ext || !d_blob)) return nfail(nd, ORL_E_INVALID, "null KeyExt references or blob");
     if (blob_bytes > 0xFFFFFFFFull) return nfail(nd, ORL_E_INVALID, "KeyExt blob of %llu bytes (<= 4 GiB)", (unsigned long long)blob_bytes);
+    if (ctx_sw_on(nd->ctx))  // the KeyExt route has no stateless-worker form: refuse rather than route such grains by the directory
+        return nfail(nd, ORL_E_STATE, "the KeyExt node route does not take stateless-worker types (orl_sw_types_set)");
     nd->kx_ext = n ? d_ext : nullptr;
     nd->kx_blob = d_blob;
     nd->kx_bytes = blob_bytes;

@@ -159,9 +159,23 @@ __device__ __forceinline__ bool encode_narrow(const RouteParams& P, const u32x4&
 // Together they mirror the oracle's route_one (Dispatcher.AddressMessage, Dispatcher.cs:555-579).
 constexpr uint32_t kNeedProbe = 0xFFFFFFFFu;
 constexpr uint32_t kNeedProbeCache = 0xFFFFFFFEu;
+// SW instantiations only: the message's type is a stateless-worker type (sw_route decides it from the local catalog).
+// Below kNeedProbeCache, so every `r >= kNeedProbeCache` test leaves it alone; the SW callers resolve it before any
+// `r < kNeedProbeCache` test reads r as a final word.
+constexpr uint32_t kStateless = 0xFFFFFFFDu;
 
+// Whether tcd is one of the context's stateless-worker types (GrainTypeData.IsStatelessWorker, GrainTypeData.cs:43-50).
+// Constant indices: the list is a kernel argument and stays in scalar registers.
+__device__ __forceinline__ bool sw_listed(const SwView& V, uint64_t tcd) {
+    bool hit = false;
+#pragma unroll
+    for (uint32_t i = 0; i < ORL_MAX_SW_TYPES; ++i) hit = hit || (i < V.n && V.tcd[i] == tcd);
+    return hit;
+}
+
+template <bool SW = false>
 __device__ __forceinline__ uint32_t route_head(const RouteParams& P, const Msg& m, bool excl_opt, uint32_t& h,
-                                               uint32_t& owner, uint32_t& rf) {
+                                               uint32_t& owner, uint32_t& rf, const SwView* sw = nullptr) {
     const uint32_t me = m.meta & 0xFFu;
     const uint32_t hflags = (m.meta >> 16) & 0xFFu;
     rf = 0;
@@ -170,6 +184,10 @@ __device__ __forceinline__ uint32_t route_head(const RouteParams& P, const Msg& 
     if (hflags & ORL_HDR_ADDRESS_COMPLETE) {  // TargetAddress.IsComplete (Dispatcher.cs:557-558)
         const uint32_t ts = m.meta >> 24;
         return pack_route(0xFFu, ts, ORL_ST_ADDRESS_COMPLETE, ts == me ? ORL_RF_LOOPBACK : 0u);
+    }
+    if (SW && sw_listed(*sw, m.tcd)) {  // never in the directory (Catalog.cs:1156-1185): no owner, no ring
+        h = (hflags & ORL_HDR_HASH_VALID) ? m.aux : jenkins3(m.tcd, m.n0, m.n1);
+        return kStateless;
     }
     const uint32_t cat = (uint32_t)(m.tcd >> 56);
     h = (hflags & ORL_HDR_HASH_VALID) ? m.aux : jenkins3(m.tcd, m.n0, m.n1);  // stage 1
@@ -264,6 +282,53 @@ __device__ __forceinline__ uint32_t route_tail(const RouteParams& P, const Msg& 
     return pack_route(owner, host, ORL_ST_NEW_PLACEMENT, rf);
 }
 
+// StatelessWorkerDirector.OnSelectActivation (StatelessWorkerDirector.cs:35-67) for a message route_head<true> marked
+// kStateless: one 64-B catalog slot of (grain, sending silo) decides it.  h = the message's hash (aux with
+// ORL_HDR_HASH_VALID), the stand-in for random.Next (:62-63).  The probe starts from the key's own uniform hash, which
+// is h unless the header carries a hash of the sender's choosing: the catalog is keyed by the grain, as the directory's
+// reference lookup is.
+//   no entry, or count == 0 (:46-47)          NEW_PLACEMENT on the sending silo (OnAddActivation, :69-74)
+//   an idle activation (:51-58)               HIT, the first idle one in list order
+//   all busy, count >= MaxLocal (:60-64)      HIT, list[count == 1 ? 0 : h % count]
+//   all busy, count < MaxLocal (:66)          NEW_PLACEMENT
+// Slot words: a = {tcd, n0}, b = {n1, silo | count << 8 | busy << 16 | state << 24, max_local}; the chosen handle is
+// read from the same line.
+__device__ __forceinline__ uint32_t sw_route(const SwView& V, const Msg& m, uint32_t h, uint32_t& act) {
+    const uint32_t me = m.meta & 0xFFu;
+    const uint32_t hflags = (m.meta >> 16) & 0xFFu;
+    const uint32_t hk = (hflags & ORL_HDR_HASH_VALID) ? jenkins3(m.tcd, m.n0, m.n1) : h;
+    const uint32_t rf = ORL_RF_STATELESS | ORL_RF_LOOPBACK;
+    act = ORL_NO_ACT;
+    if (V.table != nullptr) {
+        const u32x4* t4 = reinterpret_cast<const u32x4*>(V.table);
+        uint64_t slot = sw_start(hk, me, V.mask);
+        int st = 2;  // 0 found, 1 chain end, 2 step on
+        u32x4 b{};
+        for (uint64_t step = 0; st == 2 && step <= V.mask; ++step) {
+            const u32x4 a = t4[4 * slot];
+            b = t4[4 * slot + 1];
+            const uint32_t state = b.z >> 24;
+            if (state == SLOT_EMPTY) st = 1;
+            else if (state == SLOT_FULL && (b.z & 0xFFu) == me && a.x == (uint32_t)m.tcd && a.y == (uint32_t)(m.tcd >> 32) &&
+                     a.z == (uint32_t)m.n0 && a.w == (uint32_t)(m.n0 >> 32) && b.x == (uint32_t)m.n1 &&
+                     b.y == (uint32_t)(m.n1 >> 32)) st = 0;
+            else slot = (slot + 1) & V.mask;
+        }
+        if (st == 0) {
+            const uint32_t count = (b.z >> 8) & 0xFFu, busy = (b.z >> 16) & 0xFFu, maxl = b.w & 0xFFu;
+            const uint32_t idle = ~busy & ((1u << count) - 1u);
+            uint32_t pos = ORL_SW_MAX_LOCAL;
+            if (idle) pos = (uint32_t)__builtin_ctz(idle);
+            else if (count != 0 && count >= maxl) pos = count == 1 ? 0u : h % count;
+            if (pos < ORL_SW_MAX_LOCAL) {
+                act = V.table[slot].act[pos];
+                return pack_route(0xFFu, me, ORL_ST_HIT, rf);
+            }
+        }
+    }
+    return pack_route(0xFFu, me, ORL_ST_NEW_PLACEMENT, rf | ORL_RF_NEW_PLACEMENT);
+}
+
 // The directory cache's LRU generations (round 6): the cache table of cmask + 1 slots is followed by one
 // u64 generation per slot and the generation base G (gen[cmask + 1]).  AdaptiveGrainDirectoryCache.LookUp →
 // LRU.TryGetValue gives a found entry the next generation (LRU.cs:147-174); here a batch's lookups stamp G + their message
@@ -346,14 +411,17 @@ __device__ __forceinline__ uint32_t cached_verdict(const RouteParams& P, const M
 // straight to the rank hosting the cached activation (cact = its handle, chost = its silo), as a reference silo sends an
 // addressed message to TargetSilo (Dispatcher.cs:555-579, OutboundMessageQueue.cs:113-145).  Otherwise the owner's rank
 // (the FullLookup path, :719-765), or this rank for messages that need no directory.
+// SW: a stateless-worker message stays on this rank (route_head<true> answers kStateless before any owner or cache probe).
+template <bool SW = false>
 __device__ __forceinline__ uint32_t dest_rank_cached(const RouteParams& P, const uint8_t* __restrict__ rank_of_silo,
                                                      const DirSlot* __restrict__ cache, uint64_t cmask, const Msg& m,
                                                      bool excl_opt, uint32_t my_rank, uint32_t& cact, uint32_t& chost,
-                                                     uint32_t e) {
+                                                     uint32_t e, const SwView* sw = nullptr) {
     uint32_t h, owner, rf;
     cact = ORL_NO_ACT;
     chost = 0xFFu;
-    const uint32_t r = route_head(P, m, excl_opt, h, owner, rf);
+    const uint32_t r = route_head<SW>(P, m, excl_opt, h, owner, rf, sw);
+    if (SW && r == kStateless) return my_rank;
     if (r == kNeedProbeCache) {
         const u32x4* c4 = reinterpret_cast<const u32x4*>(cache);
         uint64_t slot = dir_slot(h, cmask);
@@ -771,17 +839,20 @@ __device__ __forceinline__ Msg pf_decode(const RouteParams& P, const u32x4* regi
 #ifndef ORL_PART_ATTR
 #define ORL_PART_ATTR
 #endif
-template <int HB, int FMT, int PW, bool CIN = false, bool LRU = false>
-__global__ __launch_bounds__(kRouteThreads) ORL_ROUTE_ATTR void k_route(const RouteParams* __restrict__ gp, const DirSlot* __restrict__ dir,
-                                                         uint64_t dmask, const DirSlot* __restrict__ cache, uint64_t cmask,
-                                                         const ProbeSlot* __restrict__ probe,
-                                                         const uint32_t* __restrict__ probe_bad,
-                                                         const void* __restrict__ in, uint32_t n,
-                                                         uint32_t excl, uint32_t* __restrict__ route,
-                                                         uint32_t* __restrict__ act_out, uint16_t* __restrict__ tile_cnt,
-                                                         uint32_t bins, uint32_t shift, uint32_t items,
-                                                         const uint32_t* __restrict__ hot_words, uint32_t* __restrict__ hot_rows,
-                                                         const uint32_t* __restrict__ in_act) {
+// SW (stateless-worker types set, round 7): route_head<true> marks a listed type's message kStateless right after the
+// address-complete test and sw_route decides it from the local catalog (`sw`: the types and the table, a kernel argument
+// of k_route_sw only); the fused histogram and the hot-key count see the chosen handle like any other.  The SW forms
+// read the 32-B `dir` table (PW = 0).  The body is shared: k_route (SW = false, sw = nullptr) compiles to what it was.
+template <int HB, int FMT, int PW, bool CIN, bool LRU, bool SW>
+__device__ __forceinline__ void route_body(const RouteParams* __restrict__ gp, const DirSlot* __restrict__ dir,
+                                           uint64_t dmask, const DirSlot* __restrict__ cache, uint64_t cmask,
+                                           const ProbeSlot* __restrict__ probe, const uint32_t* __restrict__ probe_bad,
+                                           const void* __restrict__ in, uint32_t n, uint32_t excl,
+                                           uint32_t* __restrict__ route, uint32_t* __restrict__ act_out,
+                                           uint16_t* __restrict__ tile_cnt, uint32_t bins, uint32_t shift, uint32_t items,
+                                           const uint32_t* __restrict__ hot_words, uint32_t* __restrict__ hot_rows,
+                                           const uint32_t* __restrict__ in_act, const SwView* sw) {
+    static_assert(!SW || PW == 0, "the stateless-worker forms read the 32-B directory table");
     __shared__ RouteSmem<HB> sm;
     constexpr bool HIST = HB > 0;
     // (exchange records too when ORL_ROUTE_PF=2: at a node rank's route it measured 0.586 -> 0.590 ms hot, 0.385 -> 0.396
@@ -917,8 +988,9 @@ __global__ __launch_bounds__(kRouteThreads) ORL_ROUTE_ATTR void k_route(const Ro
         }
         uint32_t cact = ORL_NO_ACT, vact = ORL_NO_ACT;
         if (e < n) {
-            r = route_head(sm.P, m, excl != 0, h, own, rf);
-            if (CIN) r = sender_cached(sm.P, m, in_act[e], h, own, rf, r, cact, vact);
+            r = route_head<SW>(sm.P, m, excl != 0, h, own, rf, sw);
+            if (SW && r == kStateless) r = sw_route(*sw, m, h, cact);  // final word; cact = the chosen handle
+            else if (CIN) r = sender_cached(sm.P, m, in_act[e], h, own, rf, r, cact, vact);
             if (r >= kNeedProbeCache) {
                 if (r == kNeedProbeCache) {  // remote owner, directory cache on
                     dir4 = reinterpret_cast<const u32x4*>(cache);
@@ -969,6 +1041,35 @@ __global__ __launch_bounds__(kRouteThreads) ORL_ROUTE_ATTR void k_route(const Ro
         store_count_row(tile_cnt + (size_t)blockIdx.x * bins, sm.hist, bins);
         if (hot_rows && threadIdx.x == 0) hot_rows[blockIdx.x] = sm.hot;
     }
+}
+
+template <int HB, int FMT, int PW, bool CIN = false, bool LRU = false>
+__global__ __launch_bounds__(kRouteThreads) ORL_ROUTE_ATTR void k_route(const RouteParams* __restrict__ gp, const DirSlot* __restrict__ dir,
+                                                         uint64_t dmask, const DirSlot* __restrict__ cache, uint64_t cmask,
+                                                         const ProbeSlot* __restrict__ probe,
+                                                         const uint32_t* __restrict__ probe_bad,
+                                                         const void* __restrict__ in, uint32_t n,
+                                                         uint32_t excl, uint32_t* __restrict__ route,
+                                                         uint32_t* __restrict__ act_out, uint16_t* __restrict__ tile_cnt,
+                                                         uint32_t bins, uint32_t shift, uint32_t items,
+                                                         const uint32_t* __restrict__ hot_words, uint32_t* __restrict__ hot_rows,
+                                                         const uint32_t* __restrict__ in_act) {
+    route_body<HB, FMT, PW, CIN, LRU, false>(gp, dir, dmask, cache, cmask, probe, probe_bad, in, n, excl, route, act_out, tile_cnt,
+                                             bins, shift, items, hot_words, hot_rows, in_act, nullptr);
+}
+
+// k_route with the stateless-worker types set: HB x FMT x (CIN, HB = 0 only) x LRU = 18 forms, all over the 32-B table.
+template <int HB, int FMT, bool CIN = false, bool LRU = false>
+__global__ __launch_bounds__(kRouteThreads) ORL_ROUTE_ATTR void k_route_sw(const RouteParams* __restrict__ gp, const DirSlot* __restrict__ dir,
+                                                            uint64_t dmask, const DirSlot* __restrict__ cache, uint64_t cmask,
+                                                            const void* __restrict__ in, uint32_t n,
+                                                            uint32_t excl, uint32_t* __restrict__ route,
+                                                            uint32_t* __restrict__ act_out, uint16_t* __restrict__ tile_cnt,
+                                                            uint32_t bins, uint32_t shift, uint32_t items,
+                                                            const uint32_t* __restrict__ hot_words, uint32_t* __restrict__ hot_rows,
+                                                            const uint32_t* __restrict__ in_act, SwView sw) {
+    route_body<HB, FMT, 0, CIN, LRU, true>(gp, dir, dmask, cache, cmask, nullptr, nullptr, in, n, excl, route, act_out, tile_cnt,
+                                           bins, shift, items, hot_words, hot_rows, in_act, &sw);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3865,11 +3966,14 @@ __global__ __launch_bounds__(kRouteThreads) void k_fanout_expand(const uint64_t*
 // Exchange partition: destination rank per message (stages 1-2 only) + per-tile rank histogram, then a
 // stable scatter of the 32-B headers.  Messages that are not directory-routed (complete, system target,
 // null owner, no seed) stay on the sending rank.
+// SW: a stateless-worker message is routed where it was sent (StatelessWorkerDirector.cs:35-80): this rank.
+template <bool SW = false>
 __device__ __forceinline__ uint32_t dest_rank(const RouteParams& P, const uint8_t* __restrict__ rank_of_silo, const Msg& m,
-                                              bool excl_opt, uint32_t my_rank) {
+                                              bool excl_opt, uint32_t my_rank, const SwView* sw = nullptr) {
     const uint32_t me = m.meta & 0xFFu;
     const uint32_t hflags = (m.meta >> 16) & 0xFFu;
     if (hflags & ORL_HDR_ADDRESS_COMPLETE) return my_rank;
+    if (SW && sw_listed(*sw, m.tcd)) return my_rank;
     const uint32_t cat = (uint32_t)(m.tcd >> 56);
     if (cat == ORL_CAT_SYSTEM_TARGET) return my_rank;
     const uint32_t h = (hflags & ORL_HDR_HASH_VALID) ? m.aux : jenkins3(m.tcd, m.n0, m.n1);
@@ -3891,10 +3995,12 @@ struct PartSmem {
     uint32_t hist[8];
 };
 
-__global__ __launch_bounds__(kRouteThreads) void k_part_digits(const RouteParams* __restrict__ gp, const uint8_t* __restrict__ ros,
-                                                               const orl_msg_hdr* __restrict__ in, uint32_t n, uint32_t excl,
-                                                               uint32_t my_rank, uint8_t* __restrict__ digits,
-                                                               uint32_t* __restrict__ tile_hist, uint32_t ntiles, uint32_t nranks) {
+template <bool SW>
+__device__ __forceinline__ void part_digits_body(const RouteParams* __restrict__ gp, const uint8_t* __restrict__ ros,
+                                                 const orl_msg_hdr* __restrict__ in, uint32_t n, uint32_t excl,
+                                                 uint32_t my_rank, uint8_t* __restrict__ digits,
+                                                 uint32_t* __restrict__ tile_hist, uint32_t ntiles, uint32_t nranks,
+                                                 const SwView* sw) {
     __shared__ PartSmem sm;
     stage_params(&sm.P, gp);
     sm.rank_of_silo[threadIdx.x] = ros[threadIdx.x];
@@ -3905,13 +4011,29 @@ __global__ __launch_bounds__(kRouteThreads) void k_part_digits(const RouteParams
         const uint32_t e = base + j * kRouteThreads + threadIdx.x;
         if (e < n) {
             const Msg m = load_hdr(in, e);
-            const uint32_t d = dest_rank(sm.P, sm.rank_of_silo, m, excl != 0, my_rank);
+            const uint32_t d = dest_rank<SW>(sm.P, sm.rank_of_silo, m, excl != 0, my_rank, sw);
             digits[e] = (uint8_t)d;
             atomicAdd(&sm.hist[d], 1u);
         }
     }
     __syncthreads();
     if (threadIdx.x < nranks) tile_hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = sm.hist[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kRouteThreads) void k_part_digits(const RouteParams* __restrict__ gp, const uint8_t* __restrict__ ros,
+                                                               const orl_msg_hdr* __restrict__ in, uint32_t n, uint32_t excl,
+                                                               uint32_t my_rank, uint8_t* __restrict__ digits,
+                                                               uint32_t* __restrict__ tile_hist, uint32_t ntiles, uint32_t nranks) {
+    part_digits_body<false>(gp, ros, in, n, excl, my_rank, digits, tile_hist, ntiles, nranks, nullptr);
+}
+
+// With the stateless-worker types set: their messages stay on the sending rank (dest_rank<true>).
+__global__ __launch_bounds__(kRouteThreads) void k_part_digits_sw(const RouteParams* __restrict__ gp, const uint8_t* __restrict__ ros,
+                                                                  const orl_msg_hdr* __restrict__ in, uint32_t n, uint32_t excl,
+                                                                  uint32_t my_rank, uint8_t* __restrict__ digits,
+                                                                  uint32_t* __restrict__ tile_hist, uint32_t ntiles, uint32_t nranks,
+                                                                  SwView sw) {
+    part_digits_body<true>(gp, ros, in, n, excl, my_rank, digits, tile_hist, ntiles, nranks, &sw);
 }
 
 __global__ __launch_bounds__(256) void k_part_scatter(const orl_msg_hdr* __restrict__ in, const uint8_t* __restrict__ digits,
@@ -4157,122 +4279,25 @@ __global__ __launch_bounds__(kRouteThreads, FMT == 8 ? ORL_PART_MINWG : 1) ORL_P
                                                            uint64_t* __restrict__ counts, uint32_t* __restrict__ wire_status,
                                                            uint32_t tbase, uint32_t epoch, const DirSlot* __restrict__ cache,
                                                            uint64_t cmask, uint32_t* __restrict__ act_out, KxArgs kx) {
-    static_assert(!KX || FMT == 32, "KeyExt strings travel beside 32-B records only");
-    __shared__ PartLbSmem sm;
-    const uint32_t rflags = rank_flags();
-    stage_params(&sm.P, gp);
-    sm.rank_of_silo[threadIdx.x] = ros[threadIdx.x];
-    if (threadIdx.x < kWaves * 8) (&sm.lb.cnt[0][0])[threadIdx.x] = 0;
-    if (threadIdx.x == 0) sm.lb.tile = atomicAdd(&state[0], 1u) - tbase;  // the ticket counter runs on across launches
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t t = sm.lb.tile;
-    const uint32_t wbase = t * kPartTile + w * (kPartItems * 64u);
-    u32x4 h0[kPartItems], h1[kPartItems];
-    uint32_t dig[kPartItems], rank[kPartItems];
-    uint2 nrec[kPartItems];  // FMT 8: the records, encoded before the ranking so the 32-B headers leave the registers
-    uint32_t cact[CACHE ? kPartItems : 1];  // CACHE: the cached handle of each message (ORL_NO_ACT: not cached)
-    uint32_t bad = 0, ncached = 0;
-    // FMT 8 loads and encodes the tile's headers in kPartGroups groups (a scheduling barrier keeps a group's loads from
-    // being hoisted above the previous group's encoding), so only one group's 32-B headers are live at a time: fewer
-    // VGPRs, more tiles resident per CU to cover the look-back's device round trips.  Wider records keep the headers.
-    constexpr uint32_t G = FMT == 8 ? kPartGroups : 1u, GI = kPartItems / G;
-#pragma unroll
-    for (uint32_t gq = 0; gq < G; ++gq) {
-#pragma unroll
-        for (uint32_t jj = 0; jj < GI; ++jj) {  // unconditional (clamped) loads: the group's in flight together
-            const uint32_t j = gq * GI + jj, e = wbase + j * 64u + lane;
-            const u32x4* sp = reinterpret_cast<const u32x4*>(in + (e < n ? e : n - 1));
-            h0[j] = __builtin_nontemporal_load(sp);
-            h1[j] = __builtin_nontemporal_load(sp + 1);
-        }
-#pragma unroll
-        for (uint32_t jj = 0; jj < GI; ++jj) {
-            const uint32_t j = gq * GI + jj;
-            dig[j] = 0;
-            if (CACHE) cact[j] = ORL_NO_ACT;
-            if (wbase + j * 64u + lane < n) {
-                Msg m;
-                m.tcd = (uint64_t)h0[j].x | ((uint64_t)h0[j].y << 32);
-                m.n0 = (uint64_t)h0[j].z | ((uint64_t)h0[j].w << 32);
-                m.n1 = (uint64_t)h1[j].x | ((uint64_t)h1[j].y << 32);
-                m.meta = h1[j].z;
-                m.aux = h1[j].w;
-                if (KX && (uint32_t)(m.tcd >> 56) == ORL_CAT_KEYEXT_GRAIN &&
-                    !(((m.meta >> 16) & 0xFFu) & (ORL_HDR_HASH_VALID | ORL_HDR_ADDRESS_COMPLETE))) {
-                    const orl_ext_ref x = kx.in[wbase + j * 64u + lane];
-                    if ((uint64_t)x.off + x.len <= kx.blob_bytes) {  // the KeyExt hash from the bytes, carried by the record
-                        m.aux = keyext_hash_dev(m.n0, m.n1, m.tcd, kx.blob + x.off, x.len);
-                        m.meta |= ORL_HDR_HASH_VALID << 16;
-                        h1[j].z = m.meta;
-                        h1[j].w = m.aux;
-                    }
-                }
-                if (CACHE) {
-                    uint32_t chost;
-                    dig[j] = dest_rank_cached(sm.P, sm.rank_of_silo, cache, cmask, m, excl != 0, my_rank, cact[j], chost,
-                                              wbase + j * 64u + lane);
-                    if (cact[j] != ORL_NO_ACT) {  // addressed: TargetSilo = the cached silo (Message.SetTargetPlacement)
-                        h1[j].z = (h1[j].z & 0x00FFFFFFu) | (chost << 24);
-                        ++ncached;
-                    }
-                } else {
-                    dig[j] = dest_rank(sm.P, sm.rank_of_silo, m, excl != 0, my_rank);
-                }
-                if (FMT == 8) {
-                    u32x4 wr;
-                    bad |= (encode_wire(h0[j], h1[j], wr) ? 0u : 1u) | (encode_narrow(sm.P, h0[j], h1[j], nrec[j]) ? 0u : 2u);
-                }
-            }
-        }
-        if (G > 1 && gq + 1 < G) __builtin_amdgcn_sched_barrier(0);
-    }
-    if (FMT == 8 && bad) atomicOr(wire_status, bad);
-    if (CACHE && __ballot(ncached != 0u) && lane == 0) atomicOr(wire_status, ORL_PART_CACHED);
-    rank_steps<3, false, kPartItems, kPartRm>(&sm.lb.cnt[w][0], dig, n > wbase ? n - wbase : 0u, rank, rflags);
-    __syncthreads();
-    lookback_ranks(sm.lb, state, nranks, ntiles, counts, nullptr, epoch, wire_status);
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kPartItems; ++j) {
-        const uint32_t e = wbase + j * 64u + lane;
-        if (e < n) {
-            const uint32_t d = dig[j];
-            const uint64_t g = (uint64_t)d * stride + sm.lb.base[d] + sm.lb.cnt[w][d] + rank[j];
-            if (FMT == 16) {
-                u32x4 wr;
-                if (!encode_wire(h0[j], h1[j], wr)) atomicOr(wire_status, 1u);
-                reinterpret_cast<u32x4*>(out)[g] = wr;
-            } else if (FMT == 8) {
-                reinterpret_cast<uint2*>(out)[g] = nrec[j];
-            } else {
-                u32x4* dp = reinterpret_cast<u32x4*>(static_cast<orl_msg_hdr*>(out) + g);
-                dp[0] = h0[j];
-                dp[1] = h1[j];
-            }
-            if (src_index) src_index[g] = e;
-            if (CACHE) act_out[g] = cact[j];
-            if (KX) {
-                orl_ext_ref r{0xFFFFFFFFu, 0xFFFFFFFFu};
-                const uint32_t hf = (h1[j].z >> 16) & 0xFFu;
-                if ((h0[j].y >> 24) == ORL_CAT_KEYEXT_GRAIN && !(hf & ORL_HDR_ADDRESS_COMPLETE)) {
-                    const orl_ext_ref x = kx.in[e];
-                    if ((uint64_t)x.off + x.len <= kx.blob_bytes) {
-                        const uint32_t o = atomicAdd(&kx.cur[d], x.len);
-                        if ((uint64_t)o + x.len <= kx.blob_cap) {
-                            uint8_t* dst = kx.blob_out + (uint64_t)d * kx.blob_cap + o;
-                            for (uint32_t b = 0; b < x.len; ++b) dst[b] = kx.blob[x.off + b];
-                            r = orl_ext_ref{o, x.len};
-                            atomicOr(wire_status, ORL_PART_KEYEXT);
-                        } else {
-                            atomicOr(wire_status, ORL_PART_EXT_FULL);
-                        }
-                    }
-                }
-                kx.out[g] = r;
-            }
-        }
-    }
+    constexpr bool kSw = false;
+    const SwView* const swp = nullptr;
+#include "part_lb_body.inc"
+}
+
+// k_part_lb with the stateless-worker types set (round 7): the same body; `sw` carries the type list.
+template <int FMT, bool CACHE, bool KX = false>
+__global__ __launch_bounds__(kRouteThreads, FMT == 8 ? ORL_PART_MINWG : 1) ORL_PART_ATTR void k_part_lb_sw(const RouteParams* __restrict__ gp, const uint8_t* __restrict__ ros,
+                                                           const orl_msg_hdr* __restrict__ in, uint32_t n, uint32_t excl,
+                                                           uint32_t my_rank, uint32_t nranks, uint64_t stride,
+                                                           void* __restrict__ out, uint32_t* __restrict__ src_index,
+                                                           uint32_t* __restrict__ state, uint32_t ntiles,
+                                                           uint64_t* __restrict__ counts, uint32_t* __restrict__ wire_status,
+                                                           uint32_t tbase, uint32_t epoch, const DirSlot* __restrict__ cache,
+                                                           uint64_t cmask, uint32_t* __restrict__ act_out, KxArgs kx,
+                                                           SwView sw) {
+    constexpr bool kSw = true;
+    const SwView* const swp = &sw;
+#include "part_lb_body.inc"
 }
 
 // The ext-ref lane of a received chunk: the references of the records from source s (plan.recv[s] records, received back
@@ -6082,7 +6107,7 @@ int launch_probe_build(const DirSlot* d_dir, uint64_t slots, const RouteParams* 
 int launch_route_bucket(const RouteParams* d_params, const DirView& dv, const void* d_in, int fmt,
                         size_t n, uint32_t opts, uint32_t n_act, uint32_t* d_route, uint32_t* d_act, uint32_t* d_order,
                         uint32_t* d_offsets, const Scratch& s, void* stream, void* ev_begin, void* ev_end,
-                        const uint32_t* d_in_act) {
+                        const uint32_t* d_in_act, const SwView* sw) {
     hipStream_t st = (hipStream_t)stream;
     const bool buckets = !(opts & ORL_OPT_NO_BUCKETS);
     const uint32_t excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) ? 1u : 0u;
@@ -6109,7 +6134,19 @@ int launch_route_bucket(const RouteParams* d_params, const DirView& dv, const vo
 #define ORL_ROUTE_C(H, W, Q, C) do { if (dv.lru) ORL_ROUTE_L(H, W, Q, C, true); else ORL_ROUTE_L(H, W, Q, C, false); } while (0)
 #define ORL_ROUTE(H, W, Q) do { if (H == 0 && d_in_act) ORL_ROUTE_C(0, W, Q, true); else ORL_ROUTE_C(H, W, Q, false); } while (0)
 #define ORL_ROUTE_W(H, Q) do { if (fmt == 16) ORL_ROUTE(H, 16, Q); else if (fmt == 8) ORL_ROUTE(H, 8, Q); else ORL_ROUTE(H, 32, Q); } while (0)  // fmt checked above
-    if (dv.probe8) {  // the route kernel takes the 8-B form (config 2: route 1.43 -> 1.30 ms)
+    if (sw && sw->n) {  // stateless-worker types set: the SW forms (32-B table), whatever probe tables are current
+        const SwView swv = *sw;
+#define ORL_ROUTE_SL(H, W, C, LR) hipLaunchKernelGGL((k_route_sw<H, W, C, LR>), dim3(nwg), dim3(kRouteThreads), 0, st, d_params,  \
+                                                 dv.dir, dv.mask, dv.cache, dv.cmask, d_in, (uint32_t)n, excl, d_route, d_act, th,  \
+                                                 bins, shift, items, hw, hr, d_in_act, swv)
+#define ORL_ROUTE_SC(H, W, C) do { if (dv.lru) ORL_ROUTE_SL(H, W, C, true); else ORL_ROUTE_SL(H, W, C, false); } while (0)
+#define ORL_ROUTE_SW(W) do { if (hist) ORL_ROUTE_SC(kMaxDigitBits, W, false); else if (d_in_act) ORL_ROUTE_SC(0, W, true);           \
+                             else ORL_ROUTE_SC(0, W, false); } while (0)
+        if (fmt == 16) ORL_ROUTE_SW(16); else if (fmt == 8) ORL_ROUTE_SW(8); else ORL_ROUTE_SW(32);
+#undef ORL_ROUTE_SW
+#undef ORL_ROUTE_SC
+#undef ORL_ROUTE_SL
+    } else if (dv.probe8) {  // the route kernel takes the 8-B form (config 2: route 1.43 -> 1.30 ms)
         const ProbeSlot* p8 = static_cast<const ProbeSlot*>(dv.probe8);
 #define ORL_ROUTE8L(H, W, C, LR) hipLaunchKernelGGL((k_route<H, W, 8, C, LR>), dim3(nwg), dim3(kRouteThreads), 0, st, d_params,   \
                                                 dv.dir, dv.mask, dv.cache, dv.cmask, p8, nullptr, d_in, (uint32_t)n, excl, d_route,  \
@@ -6277,13 +6314,17 @@ int launch_fanout_expand(const uint64_t* d_csr_off, const uint32_t* d_csr_tgt, c
 
 int launch_partition_by_owner(const RouteParams* d_params, const orl_msg_hdr* d_in, size_t n, uint32_t opts,
                               const uint8_t* d_rank_of_silo, uint32_t nranks, uint32_t my_rank, orl_msg_hdr* d_out,
-                              uint32_t* d_src_index, uint64_t* d_counts, const Scratch& s, void* stream) {
+                              uint32_t* d_src_index, uint64_t* d_counts, const Scratch& s, void* stream, const SwView* sw) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return (int)hipMemsetAsync(d_counts, 0, sizeof(uint64_t) * nranks, st);
     const uint32_t excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) ? 1u : 0u;
     const uint32_t ntiles = ceil_div(n, kTile);
-    hipLaunchKernelGGL(k_part_digits, dim3(ntiles), dim3(kRouteThreads), 0, st, d_params, d_rank_of_silo, d_in, (uint32_t)n,
-                       excl, my_rank, s.digits, s.tile_hist, ntiles, nranks);
+    if (sw && sw->n)
+        hipLaunchKernelGGL(k_part_digits_sw, dim3(ntiles), dim3(kRouteThreads), 0, st, d_params, d_rank_of_silo, d_in, (uint32_t)n,
+                           excl, my_rank, s.digits, s.tile_hist, ntiles, nranks, *sw);
+    else
+        hipLaunchKernelGGL(k_part_digits, dim3(ntiles), dim3(kRouteThreads), 0, st, d_params, d_rank_of_silo, d_in, (uint32_t)n,
+                           excl, my_rank, s.digits, s.tile_hist, ntiles, nranks);
     scan_inplace(s.tile_hist, (uint64_t)nranks * ntiles, s, st);
     hipLaunchKernelGGL(k_part_scatter, dim3(ntiles), dim3(256), 0, st, d_in, s.digits, (uint32_t)n, s.tile_hist, ntiles, nranks,
                        d_out, d_src_index);
@@ -6517,7 +6558,7 @@ int launch_partition_padded(const RouteParams* d_params, const orl_msg_hdr* d_in
                             const uint8_t* d_rank_of_silo, uint32_t nranks, uint32_t my_rank, uint64_t stride,
                             void* d_out, int fmt, uint32_t* d_src_index, uint64_t* d_counts, uint32_t* d_wire_status,
                             Scratch& s, void* stream, const DirSlot* d_cache, uint64_t cmask, uint32_t* d_act_out,
-                            const KxLanes* kxl) {
+                            const KxLanes* kxl, const SwView* sw) {
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     if (fmt != 8 && fmt != 16 && fmt != 32) return (int)hipErrorInvalidValue;
@@ -6557,7 +6598,24 @@ int launch_partition_padded(const RouteParams* d_params, const orl_msg_hdr* d_in
                                              d_in, (uint32_t)n, excl, my_rank, nranks, stride, d_out, d_src_index, L->state,      \
                                              ntiles, d_counts, d_wire_status, tbase, epoch, d_cache, cmask, d_act_out, kx)
 #define ORL_PLB(F, C) ORL_PLB3(F, C, false)
-    if (kxon) {
+#define ORL_PLS3(F, C, X) hipLaunchKernelGGL((k_part_lb_sw<F, C, X>), dim3(ntiles), dim3(kRouteThreads), 0, st, d_params,             \
+                                             d_rank_of_silo, d_in, (uint32_t)n, excl, my_rank, nranks, stride, d_out, d_src_index,     \
+                                             L->state, ntiles, d_counts, d_wire_status, tbase, epoch, d_cache, cmask, d_act_out, kx, \
+                                             *sw)
+    if (sw && sw->n) {  // stateless-worker types set: their messages stay in the self segment
+        if (kxon) {
+            if (cached) ORL_PLS3(32, true, true);
+            else ORL_PLS3(32, false, true);
+        } else if (cached) {
+            if (fmt == 16) ORL_PLS3(16, true, false);
+            else if (fmt == 8) ORL_PLS3(8, true, false);
+            else ORL_PLS3(32, true, false);
+        } else {
+            if (fmt == 16) ORL_PLS3(16, false, false);
+            else if (fmt == 8) ORL_PLS3(8, false, false);
+            else ORL_PLS3(32, false, false);
+        }
+    } else if (kxon) {
         if (cached) ORL_PLB3(32, true, true);
         else ORL_PLB3(32, false, true);
     } else if (cached) {
@@ -6569,6 +6627,7 @@ int launch_partition_padded(const RouteParams* d_params, const orl_msg_hdr* d_in
         else if (fmt == 8) ORL_PLB(8, false);
         else ORL_PLB(32, false);
     }
+#undef ORL_PLS3
 #undef ORL_PLB
 #undef ORL_PLB3
     e = hipGetLastError();
@@ -6581,6 +6640,49 @@ int launch_partition_padded(const RouteParams* d_params, const orl_msg_hdr* d_in
     }
     const hipError_t er = hipEventRecord(L->ev, st);  // a later taker on another stream waits for this launch
     return (int)(e != hipSuccess ? e : er);
+}
+
+// ActivationData running / idle transitions of catalog activations (orl_sw_set_busy_device): message i sets or clears the
+// busy bit of handle acts[i] in the list of (keys[i], silos[i]).  One atomic on the slot's word {silo, count, busy,
+// state}; the list itself is not changed here (adds and removals go through the host mirror), so the position found
+// stays valid.  An activation named twice in a batch must carry one value.
+__global__ __launch_bounds__(256) void k_sw_set_busy(SwSlot* __restrict__ table, uint64_t mask,
+                                                     const orl_grain_key* __restrict__ keys, const uint32_t* __restrict__ acts,
+                                                     const uint8_t* __restrict__ silos, const uint8_t* __restrict__ busy, uint32_t n,
+                                                     uint8_t* __restrict__ found) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const orl_grain_key k = keys[i];
+    const uint32_t silo = silos[i], act = acts[i];
+    uint64_t slot = sw_start(jenkins3(k.type_code_data, k.n0, k.n1), silo, mask);
+    uint8_t hit = 0;
+    for (uint64_t step = 0; step <= mask; ++step) {
+        const SwSlot* s = table + slot;
+        const uint32_t state = s->state;
+        if (state == SLOT_EMPTY) break;
+        if (state == SLOT_FULL && s->silo == silo && s->tcd == k.type_code_data && s->n0 == k.n0 && s->n1 == k.n1) {
+            const uint32_t count = s->count < ORL_SW_MAX_LOCAL ? s->count : ORL_SW_MAX_LOCAL;
+            for (uint32_t p = 0; p < count; ++p) {
+                if (s->act[p] != act) continue;
+                uint32_t* w = reinterpret_cast<uint32_t*>(table + slot) + 6;  // bytes 24-27: silo, count, busy, state
+                if (busy[i]) atomicOr(w, 1u << (16u + p));
+                else atomicAnd(w, ~(1u << (16u + p)));
+                hit = 1;
+                break;
+            }
+            break;
+        }
+        slot = (slot + 1) & mask;
+    }
+    if (found) found[i] = hit;
+}
+
+int launch_sw_set_busy(SwSlot* d_table, uint64_t mask, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                       const uint8_t* d_silos, const uint8_t* d_busy, size_t n, uint8_t* d_found, void* stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_sw_set_busy, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, d_table, mask, d_keys, d_acts,
+                       d_silos, d_busy, (uint32_t)n, d_found);
+    return (int)hipGetLastError();
 }
 
 }  // namespace orl

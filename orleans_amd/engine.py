@@ -558,6 +558,71 @@ class GrainDirectoryEngine:
         self._ck(self._lib.orl_cache_count(self._ctx, C.byref(n)))
         return n.value
 
+    # ---- stateless-worker grains (StatelessWorkerDirector.cs:35-80) ----
+    def set_stateless_types(self, type_code_data: Sequence[int], max_local: Sequence[int]) -> None:
+        """The [StatelessWorker] grain types with their MaxLocal (orl_sw_types_set; GrainTypeData.cs:43-50,115,
+        StatelessWorkerPlacement.cs:44-49).  An empty list turns the feature off; any change clears the catalog."""
+        t = np.asarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in type_code_data], dtype=np.uint64)
+        m = np.asarray([int(x) for x in max_local], dtype=np.int64)
+        if len(t) != len(m) or ((m < 0) | (m > 255)).any():
+            raise OrleansRouteError(L.E_INVALID, "one MaxLocal in 0..255 per type")
+        m = m.astype(np.uint8)
+        self._ck(self._lib.orl_sw_types_set(self._ctx, ptr(t) if len(t) else None, ptr(m) if len(m) else None, len(t)))
+
+    def stateless_config(self, capacity: int) -> None:
+        """Size the local catalog for `capacity` (grain, silo) entries and clear it (orl_sw_config)."""
+        self._ck(self._lib.orl_sw_config(self._ctx, int(capacity)))
+
+    def _sw_arrays(self, keys, acts, silos):
+        keys = np.ascontiguousarray(keys, dtype=L.KEY_DTYPE)
+        acts = np.ascontiguousarray(acts, dtype=np.uint32)
+        silos = np.ascontiguousarray(silos, dtype=np.uint8)
+        assert len(acts) == len(keys) and len(silos) == len(keys)
+        return keys, acts, silos
+
+    def stateless_add(self, keys: np.ndarray, acts: np.ndarray, silos: np.ndarray) -> np.ndarray:
+        """Catalog.RegisterMessageTarget of stateless-worker activations (Catalog.cs:1169-1181), in array order:
+        L.SW_ADDED / L.SW_DUPLICATE / L.SW_UNSUPPORTED per item."""
+        keys, acts, silos = self._sw_arrays(keys, acts, silos)
+        st = np.zeros(len(keys), np.uint8)
+        self._ck(self._lib.orl_sw_add(self._ctx, ptr(keys), ptr(acts), ptr(silos), len(keys), ptr(st)))
+        return st
+
+    def stateless_remove(self, keys: np.ndarray, acts: np.ndarray, silos: np.ndarray) -> np.ndarray:
+        """Activation destroy: the handle leaves its (grain, silo) list, the others keep their order (orl_sw_remove)."""
+        keys, acts, silos = self._sw_arrays(keys, acts, silos)
+        out = np.zeros(len(keys), np.uint8)
+        self._ck(self._lib.orl_sw_remove(self._ctx, ptr(keys), ptr(acts), ptr(silos), len(keys), ptr(out)))
+        return out
+
+    def stateless_set_busy(self, keys: np.ndarray, acts: np.ndarray, silos: np.ndarray, busy: np.ndarray) -> np.ndarray:
+        """ActivationData running / idle transitions (orl_sw_set_busy): found flag per item."""
+        keys, acts, silos = self._sw_arrays(keys, acts, silos)
+        busy = np.ascontiguousarray(busy, dtype=np.uint8)
+        assert len(busy) == len(keys)
+        out = np.zeros(len(keys), np.uint8)
+        self._ck(self._lib.orl_sw_set_busy(self._ctx, ptr(keys), ptr(acts), ptr(silos), ptr(busy), len(keys), ptr(out)))
+        return out
+
+    def stateless_set_busy_device(self, d_keys, d_acts, d_silos, d_busy, n: int, d_found=None, stream=None) -> None:
+        """orl_sw_set_busy_device: device arrays, one kernel on `stream`, no synchronisation."""
+        self._ck(self._lib.orl_sw_set_busy_device(self._ctx, ptr(d_keys), ptr(d_acts), ptr(d_silos), ptr(d_busy), int(n),
+                                                  ptr(d_found), ptr(stream)))
+
+    def stateless_lookup(self, keys: np.ndarray, silos: np.ndarray):
+        """(count, acts[n, 8] in list order (NO_ACT past count), busy mask) of each (grain, silo) (orl_sw_lookup_host)."""
+        keys = np.ascontiguousarray(keys, dtype=L.KEY_DTYPE)
+        silos = np.ascontiguousarray(silos, dtype=np.uint8)
+        n = len(keys)
+        cnt, acts, busy = np.zeros(n, np.uint8), np.zeros((n, L.SW_MAX_LOCAL), np.uint32), np.zeros(n, np.uint8)
+        self._ck(self._lib.orl_sw_lookup_host(self._ctx, ptr(keys), ptr(silos), n, ptr(cnt), ptr(acts), ptr(busy)))
+        return cnt, acts, busy
+
+    def stateless_count(self) -> int:
+        n = C.c_uint64()
+        self._ck(self._lib.orl_sw_count(self._ctx, C.byref(n)))
+        return n.value
+
     # ---- outbound queues / client buckets (SURVEY §8(f) f4) ----
     def set_silo_hash(self, silo: int, consistent_hash: int) -> None:
         self._ck(self._lib.orl_silo_hash_set(self._ctx, int(silo), int(consistent_hash)))

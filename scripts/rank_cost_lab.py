@@ -12,6 +12,11 @@ of the Zipf stream whose directory entry another rank holds (a warm cache: the e
 LocalGrainDirectory.cs:761-762; the reference's default capacity is 1M, GlobalConfiguration.cs:413,417); hop 1 then
 addresses those messages at the sender (orl_partition_cached_device) and the owner routes its received records with the
 act lane (orl_route_received_device: no probe for addressed ones) before stage 4 (orl_bucket_device).
+
+LAB_SW=1 (round 7): config 3's Zipf-hot grain is a stateless-worker grain (StatelessWorkerDirector.cs:35-80) with one idle
+activation on every silo: its messages carry a stateless-worker type, hop 1 keeps them on the sending rank
+(k_part_lb_sw) and each rank routes them from its local catalog (k_route_sw).  LAB_CPU=1: only the owned-message
+imbalance (max / mean over ranks), computed on the CPU at LAB_CPU_MSGS messages (default 8M), with and without it.
 """
 import sys
 import time
@@ -40,20 +45,50 @@ def timed(fn, reps=5):
     return float(np.median(ts))
 
 
+SW_TCD = (L.CAT_GRAIN << 56) | 0x5157  # the hot grain's class with LAB_SW=1: a [StatelessWorker] type, MaxLocal 1
+
+
+def owned_imbalance_cpu(R, n_grains, n_msgs):
+    """max / mean of the messages each rank owns after hop 1, as the directory routes them and with the Zipf-hot grain a
+    stateless worker (its messages stay on their sender's rank)."""
+    cl = W.balanced_cluster()
+    ros = rank_of_silo(cl.n_silos, R)
+    m = W.zipf_messages(cl, n_grains, n_msgs)
+    ids, cnt = np.unique(m["n1"], return_counts=True)
+    hot = ids[np.argmax(cnt)]
+    dest = ros[cl.owner_of(W.jenkins3_np(m["tcd"], m["n0"], m["n1"]))]
+    out = []
+    for sw in (False, True):
+        d = np.where(m["n1"] == hot, ros[m["sending_silo"]], dest) if sw else dest
+        owned = np.bincount(d, minlength=R)
+        out.append(owned.max() / owned.mean())
+        print(f"{'stateless-worker hot grain' if sw else 'directory routing'}: owned per rank (k) "
+              f"{[int(x) // 1000 for x in owned]}, max/mean {out[-1]:.3f} (hot grain {cnt.max() / n_msgs:.3f} of {n_msgs})",
+              flush=True)
+    return out
+
+
 def main(R=8, chunks=4, width=8):
     import os
     if os.environ.get("LAB_LIB"):  # A/B: an experimental build of the library
         L.LIB_PATH = os.path.abspath(os.environ["LAB_LIB"])
     n_grains, n_total = 16_000_000, 256 << 20
+    if os.environ.get("LAB_CPU"):
+        owned_imbalance_cpu(R, n_grains, int(os.environ.get("LAB_CPU_MSGS", str(8 << 20))))
+        return
     n_msgs = n_total // R
     cl = W.balanced_cluster()
     ros = rank_of_silo(cl.n_silos, R)
     keys, uni, owner, reg = W.grain_population(cl, n_grains)
     ztab = W.zipf_tables(torch, n_grains, W.SEED_C3)
-    import os
     n_cache = int(os.environ.get("LAB_CACHE", "0"))
+    sw = bool(os.environ.get("LAB_SW"))
+    hot_id = int(ztab[1][0].item())  # Zipf rank 1 -> grain perm[0]
+    wire_types = [W.grain_tcd(cl)] + ([SW_TCD] if sw else [])
     part = GrainDirectoryEngine(n_act=1 << 24, dir_capacity=1, max_batch=n_msgs, device=0)
     W.setup_engine(part, cl)
+    if sw:
+        part.set_stateless_types([SW_TCD], [1])
     if n_cache:  # each grain's handle at its owner rank (W.register_population(dense_local=True) per rank)
         hnd = np.zeros(n_grains, np.uint32)
         orank = ros[owner]
@@ -67,7 +102,7 @@ def main(R=8, chunks=4, width=8):
     torch.cuda.set_stream(torch.cuda.Stream())
     st = torch.cuda.current_stream().cuda_stream
     if width == 8:
-        part.set_wire_types([W.grain_tcd(cl)])
+        part.set_wire_types(wire_types)
     partition = part.partition_narrow_device if width == 8 else part.partition_compact_device
     cap = n_msgs + n_msgs // 2
     d_out = torch.empty(R * cap * width, dtype=torch.uint8, device="cuda")
@@ -82,6 +117,10 @@ def main(R=8, chunks=4, width=8):
     for s in range(R):
         m = W.device_messages(torch, cl, n_grains, n_msgs, W.SEED_C3, start=s * n_msgs,
                               sender_silos=local_silos(cl.n_silos, R, s), zipf=ztab)
+        if sw:  # the hot grain's messages carry the stateless-worker type (header words 0-1: TypeCodeData)
+            hot = (m[:, 4] == hot_id) & (m[:, 5] == 0)
+            m[hot, 0] = SW_TCD & 0xFFFFFFFF
+            m[hot, 1] = SW_TCD >> 32
         step = n_msgs // chunks
         if n_cache:  # rank s's warm cache: the n_cache hottest grains owned by other ranks
             mine_s = local_silos(cl.n_silos, R, s)
@@ -132,11 +171,20 @@ def main(R=8, chunks=4, width=8):
         mask = np.zeros(cl.n_silos, np.uint8)
         mask[mine] = 1
         n_act = max(1, int((reg & mask[owner].astype(bool)).sum()))
-        eng = GrainDirectoryEngine(n_act=n_act, dir_capacity=n_act, max_batch=n, device=0)
+        n_dir = n_act
+        n_act += len(mine) if sw else 0  # + the hot grain's activation on each of the rank's silos
+        eng = GrainDirectoryEngine(n_act=n_act, dir_capacity=n_dir, max_batch=n, device=0)
         W.setup_engine(eng, cl, local_silos=mine)
         if width == 8:
-            eng.set_wire_types([W.grain_tcd(cl)])
+            eng.set_wire_types(wire_types)
         W.register_population(eng, keys, owner, reg, mask, dense_local=True)
+        if sw:  # one idle activation of the hot grain per silo of this rank
+            eng.set_stateless_types([SW_TCD], [1])
+            eng.stateless_config(16)
+            hk = np.zeros(len(mine), L.KEY_DTYPE)
+            hk["tcd"], hk["n1"] = SW_TCD, hot_id
+            st_sw = eng.stateless_add(hk, n_dir + np.arange(len(mine)), np.asarray(mine, np.uint8))
+            assert (st_sw == L.SW_ADDED).all()
         route = torch.empty(n, dtype=torch.int32, device="cuda")
         act = torch.empty(n, dtype=torch.int32, device="cuda")
         order_o = torch.empty(n, dtype=torch.int32, device="cuda")
