@@ -399,7 +399,8 @@ int orl_route_keyext_device(orl_ctx* ctx, const orl_msg_hdr* d_in, size_t n, uin
  * exchange delivers such messages to the host rank, whose stage 4 buckets them; in a single context they share the
  * unresolved bucket when the handle is >= n_act).
  * AddOrUpdate: the batch's last writer of a key wins.  Remove = CACHE_INVALIDATION_HEADER handling
- * (InsideGrainClient.cs:298-308).  Expiry / size policy (the maintainer) stays with the host: remove or clear. */
+ * (InsideGrainClient.cs:298-308).  Expiry (the maintainer) stays with the host: remove or clear; the size policy
+ * (LRU eviction at capacity) runs on the device, see below. */
 #define ORL_RF_CACHED 0x08u
 /* A record the sender addressed from a stale cache entry, re-addressed by the receiver's directory (orl_route_received_device,
  * the node exchange): the reference's NonExistentActivation forward with the old address in the cache-invalidation header
@@ -411,6 +412,30 @@ int orl_cache_add_or_update_device(orl_ctx* ctx, const orl_grain_key* d_keys, co
                                    size_t n, void* stream);
 int orl_cache_remove_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, uint8_t* d_removed, void* stream);
 int orl_cache_count(orl_ctx* ctx, uint64_t* n_out);
+/* Size policy on the device.  The reference's cache holds MaximumSize entries (1M by default) and is full in steady
+ * state, so every AddOrUpdate is an add at capacity: LRU.Add runs AdjustSize first, which frees the entry of the smallest
+ * generation while Count >= MaximumSize (src/Orleans/Utils/LRU.cs:104-116,188-205, as AdaptiveGrainDirectoryCache.cs:97-133
+ * uses it), and an update at full capacity can free the very key it updates.  orl_cache_add_or_update_device computes
+ * exactly that, entry by entry in batch order, on the caller's stream: it never synchronises the device and copies
+ * nothing to the host, whether the batch overflows the capacity, is larger than the cache, or the table has filled with
+ * tombstones (those are compacted into a second table, on the same stream).
+ * orl_cache_stats: a query (it synchronises the device like orl_cache_count).  ORL_E_STATE, with the fields filled in,
+ * when a device kernel raised the cache's error word (a table without a free slot, a violated invariant).
+ * orl_cache_evict_mode: ORL_CACHE_EVICT_DEVICE (the default) or ORL_CACHE_EVICT_HOST, which handles an add that may
+ * overflow as releases before this one did — exact counters read back, then the LRU on the host over the downloaded table:
+ * for A/B measurements and cross-checks; every such add counts as a host fallback. */
+#define ORL_CACHE_EVICT_DEVICE 0u
+#define ORL_CACHE_EVICT_HOST 1u
+struct orl_cache_stats {
+    uint64_t entries;        /* live entries */
+    uint64_t tombstones;     /* slots freed by an eviction or a removal and not reused yet */
+    uint64_t evictions;      /* entries AdjustSize freed since orl_cache_config */
+    uint64_t evict_batches;  /* adds that took the device eviction path */
+    uint64_t rebuilds;       /* tombstone compactions on the device */
+    uint64_t host_fallbacks; /* adds handled by the host LRU (ORL_CACHE_EVICT_HOST only) */
+};
+int orl_cache_stats(orl_ctx* ctx, struct orl_cache_stats* out);
+int orl_cache_evict_mode(orl_ctx* ctx, uint32_t mode);
 
 /* ---- stateless-worker grains (StatelessWorkerDirector, src/OrleansRuntime/Placement/StatelessWorkerDirector.cs:35-80)
  * A [StatelessWorker] grain is never registered in the grain directory (Catalog.cs:1156-1185, singleActivationMode =

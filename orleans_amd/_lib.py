@@ -55,6 +55,7 @@ MAX_SW_TYPES = 8
 SW_MAX_LOCAL = 8
 SW_ADDED, SW_DUPLICATE, SW_UNSUPPORTED = 0, 1, 2
 RING_CONSISTENT, RING_VBUCKETS = 0, 1
+CACHE_EVICT_DEVICE, CACHE_EVICT_HOST = 0, 1
 OUTQ_LOOPBACK, OUTQ_PING, OUTQ_SYSTEM, OUTQ_REJECT, OUTQ_OVERFLOW, OUTQ_UNKNOWN_SILO = (
     0xFFFFFFF0, 0xFFFFFFF1, 0xFFFFFFF2, 0xFFFFFFF3, 0xFFFFFFF4, 0xFFFFFFF5)
 DEC_OK, DEC_UNSUPPORTED, DEC_MALFORMED, DEC_UNKNOWN_SILO, DEC_NO_TARGET, DEC_NO_SENDER = 0, 1, 2, 3, 4, 5
@@ -117,6 +118,11 @@ class orl_node_stats(C.Structure):
     _fields_ = [("comm_count", C.c_uint32), ("chunks", C.c_uint32), ("bytes_sent", C.c_uint64 * NODE_MAX_RANKS),
                 ("host_wait_us", C.c_uint64), ("host_waits", C.c_uint64), ("exchange_mode", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class orl_cache_stats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("tombstones", C.c_uint64), ("evictions", C.c_uint64),
+                ("evict_batches", C.c_uint64), ("rebuilds", C.c_uint64), ("host_fallbacks", C.c_uint64)]
 
 
 class orl_node_chunk_plan(C.Structure):
@@ -205,6 +211,8 @@ _SIGS = {
     "orl_cache_add_or_update_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
     "orl_cache_remove_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
     "orl_cache_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "orl_cache_stats": (C.c_int, [_P, _P]),
+    "orl_cache_evict_mode": (C.c_int, [_P, C.c_uint32]),
     "orl_sw_types_set": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "orl_sw_config": (C.c_int, [_P, C.c_uint64]),
     "orl_sw_add": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),

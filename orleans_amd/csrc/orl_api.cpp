@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "orl_internal.h"
+#include "cache_evict.h"
 
 using namespace orl;
 
@@ -246,7 +247,11 @@ struct orl_ctx {
     // directory cache (AdaptiveGrainDirectoryCache, f4): device table of remote-owned grains
     DirSlot* d_cache = nullptr;
     uint32_t* d_cclaim = nullptr;
-    uint64_t* d_cstate = nullptr;    // {entries, tombstones, error flag}
+    uint64_t* d_cstate = nullptr;    // {entries, tombstones, error word, cumulative device evictions}
+    DirSlot* d_cache2 = nullptr;     // the second table a tombstone compaction rebuilds into (then the two swap)
+    CacheEvictScratch cev;           // scratch of the device eviction (cache_evict.hip), sized by orl_cache_config
+    uint32_t cache_mode = ORL_CACHE_EVICT_DEVICE;
+    uint64_t cache_host_evictions = 0, cache_evict_batches = 0, cache_rebuilds = 0, cache_host_fallbacks = 0;
     uint64_t cache_slots = 0, cache_ub = 0, cache_tombs_ub = 0;
     uint64_t cache_cap = 0;       // LRU.MaximumSize (orl_cache_config's capacity)
     uint64_t cache_gen_free = 0;  // LRU.generationToFree: the generation of the last entry evicted
@@ -758,7 +763,7 @@ int ensure_staging(orl_ctx* c, size_t in_bytes, size_t out_words) {
 
 void free_device(orl_ctx* c) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
-    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
+    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
     f(c->s.pairs_a); f(c->s.pairs_b); f(c->s.idx_a); f(c->s.sorted_keys); f(c->s.tile_hist); f(c->s.tile_cnt); f(c->s.scan_sums); f(c->s.digits); f(c->s.col_sums); f(c->s.col_tot); f(c->s.seg_hist); f(c->s.seg_carry); f(c->s.seg_meta); f(c->s.seg_lb); f(c->s.seg_lbctl); f(c->s.bstart); f(c->s.sstart); f(c->s.gap_q); f(c->s.hot); f(c->s.hot_rows); f(c->s.hot_bmax); f(c->s.pick_word); f(c->s.fan_blk); f(c->s.lsd_hot);
     for (auto& L : c->s.lb) {
         f(L.state);
@@ -2078,12 +2083,17 @@ int orl_cache_config(orl_ctx* c, uint64_t capacity) {
     if (capacity == 0) return fail(c, ORL_E_INVALID, "capacity must be >= 1");
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     ORL_HIP(c, hipDeviceSynchronize());
-    (void)hipFree(c->d_cache); (void)hipFree(c->d_cclaim); (void)hipFree(c->d_cstate);
-    c->d_cache = nullptr; c->d_cclaim = nullptr; c->d_cstate = nullptr;
+    (void)hipFree(c->d_cache); (void)hipFree(c->d_cache2); (void)hipFree(c->d_cclaim); (void)hipFree(c->d_cstate);
+    c->d_cache = nullptr; c->d_cache2 = nullptr; c->d_cclaim = nullptr; c->d_cstate = nullptr;
+    cache_evict_free(&c->cev);
+    c->cache_slots = 0;
     const uint64_t slots = next_pow2(2 * capacity);
     // the table, then one u64 LRU generation per slot and the generation base (route_kernels.hip cache_gens)
     const size_t bytes = slots * sizeof(DirSlot) + (slots + 1) * 8;
     ORL_HIP(c, hipMalloc((void**)&c->d_cache, bytes));
+    ORL_HIP(c, hipMalloc((void**)&c->d_cache2, bytes));
+    ORL_HIP(c, hipMemset(c->d_cache2, 0, bytes));
+    if (int e = cache_evict_alloc(&c->cev, c->s.max_batch, slots)) return hipfail(c, (hipError_t)e, "cache eviction scratch");
     ORL_HIP(c, hipMalloc((void**)&c->d_cclaim, slots * 4));
     ORL_HIP(c, hipMalloc((void**)&c->d_cstate, 32));
     ORL_HIP(c, hipMemset(c->d_cache, 0, bytes));
@@ -2093,6 +2103,7 @@ int orl_cache_config(orl_ctx* c, uint64_t capacity) {
     c->cache_cap = capacity;
     c->cache_gen_free = 0;
     c->cache_ub = c->cache_tombs_ub = 0;
+    c->cache_host_evictions = c->cache_evict_batches = c->cache_rebuilds = c->cache_host_fallbacks = 0;
     set_cache_on(c, false);
     return ORL_OK;
 }
@@ -2102,7 +2113,7 @@ int orl_cache_clear(orl_ctx* c) {  // LRU.Clear: the entries go, the generation 
     if (!c->cache_slots) return ORL_OK;
     ORL_HIP(c, hipDeviceSynchronize());
     ORL_HIP(c, hipMemset(c->d_cache, 0, c->cache_slots * sizeof(DirSlot)));
-    ORL_HIP(c, hipMemset(c->d_cstate, 0, 32));
+    ORL_HIP(c, hipMemset(c->d_cstate, 0, 24));  // the cumulative eviction count runs on
     c->cache_ub = c->cache_tombs_ub = 0;
     set_cache_on(c, false);
     return ORL_OK;
@@ -2153,6 +2164,7 @@ int cache_add_host_lru(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* 
         while (ents.size() >= c->cache_cap && !by_gen.empty()) {  // AdjustSize
             auto v = by_gen.begin();
             c->cache_gen_free = v->first;
+            ++c->cache_host_evictions;
             ents.erase(v->second);
             by_gen.erase(v);
         }
@@ -2189,9 +2201,14 @@ int cache_add_host_lru(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* 
 }
 }  // namespace
 
-// LRU.Add per entry in batch order.  No entry can be evicted while the cache holds <= capacity - n entries before the batch
-// (every add then finds Count < MaximumSize): the device path (the batch's last writer of a key wins, its generation
-// stamped).  Otherwise the exact sequential LRU on the host (cache_add_host_lru).
+// LRU.Add per entry in batch order, on the caller's stream.  No entry can be evicted while the cache holds <= capacity - n
+// entries before the batch (every add then finds Count < MaximumSize): the plain update (the batch's last writer of a key
+// wins, its generation stamped).  When the host's upper bounds say an eviction is possible, the exact sequential LRU as one
+// preparation, one serial pass and one apply on the device (cache_evict.hip); when they say the table's load (entries +
+// tombstones + new entries) could pass 7/8, a tombstone compaction into the second table first — between the tombstoning
+// and the inserts of an evicting batch, so that even a batch larger than the cache ends with load <= 1/2.  No device-wide
+// sync, no copy to the host.  ORL_CACHE_EVICT_HOST keeps the earlier path (exact counters read back, then the LRU on the
+// host) for A/B runs and as the tests' cross-check.
 int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
                                    size_t n, void* stream) {
     if (!c) return ORL_E_INVALID;
@@ -2205,16 +2222,49 @@ int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, cons
     if (r) return r;
     set_cache_on(c, true);
     if ((r = sync_device_state(c))) return r;
-    if (!fits(c->cache_ub, c->cache_tombs_ub)) {  // exact counters (a sync)
-        ORL_HIP(c, hipDeviceSynchronize());
-        uint64_t stw[3];
-        ORL_HIP(c, hipMemcpy(stw, c->d_cstate, sizeof stw, hipMemcpyDeviceToHost));
-        c->cache_ub = stw[0];
-        c->cache_tombs_ub = stw[1];
-        if (!fits(c->cache_ub, c->cache_tombs_ub)) return cache_add_host_lru(c, d_keys, d_acts, d_silos, n);
-    }
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_cache_update(c->d_cache, c->cache_slots - 1, c->d_cclaim, c->d_cstate, d_keys, d_acts, d_silos, n, c->cfg.n_act,
+    const uint64_t mask = c->cache_slots - 1;
+    if (!fits(c->cache_ub, c->cache_tombs_ub)) {
+        if (c->cache_mode == ORL_CACHE_EVICT_HOST) {  // exact counters (a sync), then the host LRU if still needed
+            ORL_HIP(c, hipDeviceSynchronize());
+            uint64_t stw[3];
+            ORL_HIP(c, hipMemcpy(stw, c->d_cstate, sizeof stw, hipMemcpyDeviceToHost));
+            c->cache_ub = stw[0];
+            c->cache_tombs_ub = stw[1];
+            if (!fits(c->cache_ub, c->cache_tombs_ub)) {
+                ++c->cache_host_fallbacks;
+                return cache_add_host_lru(c, d_keys, d_acts, d_silos, n);
+            }
+        } else {
+            if (n == 0) return ORL_OK;
+            const uint64_t fresh_ub = std::min<uint64_t>(n, c->cache_cap);  // the batch leaves at most capacity entries
+            const bool evicts = c->cache_ub + n > c->cache_cap;
+            const bool crowded = (c->cache_ub + c->cache_tombs_ub + (evicts ? fresh_ub : n)) * 8 > c->cache_slots * 7;
+            if (evicts) {
+                int e = launch_cache_evict_add(c->d_cache, mask, crowded ? c->d_cache2 : nullptr, c->d_cstate, c->cache_cap, d_keys,
+                                               d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st);
+                if (e) return hipfail(c, (hipError_t)e, "cache eviction launch");
+                ++c->cache_evict_batches;
+                // FULL + TOMB slots grow by at most the new entries (an eviction turns a FULL slot into a tombstone)
+                const uint64_t occupied = c->cache_ub + c->cache_tombs_ub + fresh_ub;
+                c->cache_ub = std::min(c->cache_ub + n, c->cache_cap);
+                c->cache_tombs_ub = occupied > c->cache_ub ? occupied - c->cache_ub : 0;
+                if (crowded) {  // compacted after the tombstoning: what is left is the batch's result, no tombstones
+                    std::swap(c->d_cache, c->d_cache2);
+                    ++c->cache_rebuilds;
+                    c->cache_tombs_ub = 0;
+                }
+                return ORL_OK;
+            }
+            // no eviction possible, only tombstones in the way: compact, then the plain update below
+            int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st);
+            if (e) return hipfail(c, (hipError_t)e, "cache rebuild launch");
+            std::swap(c->d_cache, c->d_cache2);
+            ++c->cache_rebuilds;
+            c->cache_tombs_ub = 0;
+        }
+    }
+    int e = launch_cache_update(c->d_cache, mask, c->d_cclaim, c->d_cstate, d_keys, d_acts, d_silos, n, c->cfg.n_act,
                                 c->n_silos, c->d_dslot, c->d_dflag, reinterpret_cast<uint32_t*>(c->d_cstate + 2), st, c->d_params);
     if (e) return hipfail(c, (hipError_t)e, "cache update launch");
     c->cache_ub += n;
@@ -2230,6 +2280,32 @@ int orl_cache_remove_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, u
     int e = launch_dir_remove(c->d_cache, c->cache_slots - 1, c->d_cclaim, c->d_cstate, d_keys, n, c->d_dslot, d_removed, st);
     if (e) return hipfail(c, (hipError_t)e, "cache remove launch");
     c->cache_tombs_ub += n;
+    return ORL_OK;
+}
+
+int orl_cache_stats(orl_ctx* c, struct orl_cache_stats* out) {
+    if (!c || !out) return ORL_E_INVALID;
+    *out = {};
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
+    ORL_HIP(c, hipDeviceSynchronize());
+    uint64_t st[4];
+    ORL_HIP(c, hipMemcpy(st, c->d_cstate, sizeof st, hipMemcpyDeviceToHost));
+    out->entries = st[0];
+    out->tombstones = st[1];
+    out->evictions = st[3] + c->cache_host_evictions;
+    out->evict_batches = c->cache_evict_batches;
+    out->rebuilds = c->cache_rebuilds;
+    out->host_fallbacks = c->cache_host_fallbacks;
+    if ((uint32_t)st[2]) return fail(c, ORL_E_STATE, "directory cache: the device raised error word 0x%x", (unsigned)(uint32_t)st[2]);
+    return ORL_OK;
+}
+
+int orl_cache_evict_mode(orl_ctx* c, uint32_t mode) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (mode != ORL_CACHE_EVICT_DEVICE && mode != ORL_CACHE_EVICT_HOST) return fail(c, ORL_E_INVALID, "unknown eviction mode %u", mode);
+    c->cache_mode = mode;
     return ORL_OK;
 }
 

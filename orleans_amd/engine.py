@@ -558,6 +558,18 @@ class GrainDirectoryEngine:
         self._ck(self._lib.orl_cache_count(self._ctx, C.byref(n)))
         return n.value
 
+    def cache_stats(self) -> dict:
+        """The cache's counters (orl_cache_stats; synchronises the device): entries, tombstones, evictions,
+        evict_batches, rebuilds, host_fallbacks.  Raises with E_STATE if a device kernel raised the cache's error word."""
+        st = L.orl_cache_stats()
+        self._ck(self._lib.orl_cache_stats(self._ctx, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
+
+    def cache_evict_mode(self, mode: int) -> None:
+        """Where an add that may overflow the capacity runs: L.CACHE_EVICT_DEVICE (the default, stream-ordered) or
+        L.CACHE_EVICT_HOST (the exact LRU on the host over the table read back: for A/B runs and cross-checks)."""
+        self._ck(self._lib.orl_cache_evict_mode(self._ctx, int(mode)))
+
     # ---- stateless-worker grains (StatelessWorkerDirector.cs:35-80) ----
     def set_stateless_types(self, type_code_data: Sequence[int], max_local: Sequence[int]) -> None:
         """The [StatelessWorker] grain types with their MaxLocal (orl_sw_types_set; GrainTypeData.cs:43-50,115,
