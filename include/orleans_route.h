@@ -399,8 +399,10 @@ int orl_route_keyext_device(orl_ctx* ctx, const orl_msg_hdr* d_in, size_t n, uin
  * exchange delivers such messages to the host rank, whose stage 4 buckets them; in a single context they share the
  * unresolved bucket when the handle is >= n_act).
  * AddOrUpdate: the batch's last writer of a key wins.  Remove = CACHE_INVALIDATION_HEADER handling
- * (InsideGrainClient.cs:298-308).  Expiry (the maintainer) stays with the host: remove or clear; the size policy
- * (LRU eviction at capacity) runs on the device, see below. */
+ * (InsideGrainClient.cs:298-308).  The size policy (LRU eviction at capacity) runs on the device, see below.  A cache
+ * configured with orl_cache_config is the reference's LRUBasedGrainDirectoryCache: nothing expires.  Expiry, ETags and
+ * the maintainer (DirectoryCachingStrategyType.Adaptive, the reference's default) are the adaptive mode further below
+ * (orl_cache_config_adaptive), and they run on the device too. */
 #define ORL_RF_CACHED 0x08u
 /* A record the sender addressed from a stale cache entry, re-addressed by the receiver's directory (orl_route_received_device,
  * the node exchange): the reference's NonExistentActivation forward with the old address in the cache-invalidation header
@@ -436,6 +438,70 @@ struct orl_cache_stats {
 };
 int orl_cache_stats(orl_ctx* ctx, struct orl_cache_stats* out);
 int orl_cache_evict_mode(orl_ctx* ctx, uint32_t mode);
+
+/* Adaptive mode: AdaptiveGrainDirectoryCache's per-entry state (ETag, ExpirationTimer, LastRefreshed, NumAccesses:
+ * AdaptiveGrainDirectoryCache.cs:32-70) beside the device table, and AdaptiveDirectoryCacheMaintainer on the device.
+ * Time is always the caller's `now_ticks` (.NET ticks of 100 ns, standing in for DateTime.UtcNow): the library reads no
+ * clock.  "Accessed" (NumAccesses != 0, the only test the reference makes of it) means: looked up by a route or partition
+ * call since the entry was added, marked fresh while unaccessed, or listed by a sweep.  Every call below needs a device
+ * context and, except orl_cache_config_adaptive and orl_cache_peek_device, an adaptive cache (ORL_E_STATE otherwise); each
+ * runs on the caller's stream without a device-wide sync or a copy to the host.  As for the LRU stamps, the calls that
+ * touch one cache must be ordered on one stream.
+ *
+ * orl_cache_config_adaptive: orl_cache_config plus the state above.  The reference's defaults (GlobalConfiguration.cs:
+ *   413-417) are 1,000,000 entries, 30 s, 240 s and 2.0.  ORL_E_INVALID unless 0 <= initial <= max <= 2^61, growth is
+ *   finite and >= 0 and (double)max * growth < 2^63 (what keeps the reference's checked arithmetic from throwing).
+ *   ORL_CACHE_EVICT_HOST is refused on an adaptive cache (ORL_E_STATE); configuring one resets the mode to DEVICE.
+ * orl_cache_add_or_update_versioned_device: AddOrUpdate(key, value, version) (:97-103), entry by entry like
+ *   orl_cache_add_or_update_device (fit / evict / compact).  The surviving last writer of a key gets its etag, the initial
+ *   timer, LastRefreshed = now and NumAccesses = 0.  orl_cache_add_or_update_device on an adaptive cache is the same with
+ *   etag 0 and the last now_ticks the context was given.
+ * orl_cache_maintain_device: one pass of AdaptiveDirectoryCacheMaintainer.Run (AdaptiveDirectoryCacheMaintainer.cs:54-143)
+ *   over every entry.  Its owner is CalculateTargetSilo as the route calls compute it for sender `me` with
+ *   opts & ORL_OPT_EXCLUDE_IF_STOPPING.  Owner null: skipped.  Owner's partition held by this context (local[], the
+ *   generalisation of owner.Equals(MyAddress)): removed.  now < LastRefreshed + ExpirationTimer: kept (an entry expires AT
+ *   the boundary).  Expired and not accessed: removed.  Expired and accessed: (grain, etag) goes to its owner's refresh
+ *   list, its access mark is reset and, as BuildGrainAndETagList's cache.Get does (:216-238), it becomes the most recently
+ *   used entry: list position p takes LRU generation G + p + 1.  *out (host memory) receives device pointers into buffers
+ *   the context owns (sized at configuration, so nothing can overflow; valid until the next maintain call or
+ *   configuration): owner o's list is [d_owner_offsets[o], d_owner_offsets[o + 1]) of d_keys / d_etags, owners in ascending
+ *   silo index, table-slot order inside an owner (deterministic for a given table).  Send each list as the owner's
+ *   LookUpMany request.
+ * orl_cache_mark_fresh_device: MarkAsFresh (:150-159) per key; the keys of a batch must be distinct (a refresh response
+ *   names a grain once).  A found key gets ExpirationTimer = min(max, (int64)((double)timer * growth)), LastRefreshed = now,
+ *   and is most recently used; its access mark is unchanged.  d_found[i] (optional) = 1 / 0.
+ * orl_cache_adjust_for_removed_silo_device: LocalGrainDirectory.AdjustLocalCache (LocalGrainDirectory.cs:330-344), to be
+ *   called after orl_ring_remove_server: removes the entries whose owner's partition this context now holds and those whose
+ *   activation sits on removed_silo.  *d_removed_count (optional, device u64) = how many.  Works on a plain cache too.
+ * orl_cache_peek_device: the entries of n keys without an LRU stamp and without an access (the role of KeyValues); a miss
+ *   gives act ORL_NO_ACT, silo ORL_NULL_SILO, etag ORL_CACHE_NO_ETAG.  Every output is optional; the last four need an
+ *   adaptive cache.
+ *
+ * ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) on the host: split the owner's response into
+ * maximal runs of one kind and issue them in order — an activation list returned: orl_cache_add_or_update_versioned_device
+ * with the returned etag; etag -1 and no list: orl_cache_remove_device; an etag only: orl_cache_mark_fresh_device.  That is
+ * the reference's sequential loop.  The owner's side of the exchange (RemoteGrainDirectory.LookUpMany) needs a version tag
+ * per directory entry, which the partition table does not hold: it stays with the host. */
+#define ORL_CACHE_NO_ETAG (-1) /* GrainInfo.NO_ETAG */
+struct orl_cache_sweep {
+    const orl_grain_key* d_keys;      /* the refresh lists, owner-major */
+    const int32_t* d_etags;
+    const uint32_t* d_owner_offsets;  /* n_silos + 1 */
+    const uint64_t* d_counts;         /* {self-owned removed, kept, expired removed, to refresh, skipped (owner null)} */
+};
+int orl_cache_config_adaptive(orl_ctx* ctx, uint64_t capacity, int64_t initial_ttl_ticks, int64_t max_ttl_ticks,
+                              double ttl_growth);
+int orl_cache_add_or_update_versioned_device(orl_ctx* ctx, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                                             const uint8_t* d_silos, const int32_t* d_etags, size_t n, int64_t now_ticks,
+                                             void* stream);
+int orl_cache_maintain_device(orl_ctx* ctx, uint32_t me, uint32_t opts, int64_t now_ticks, struct orl_cache_sweep* out,
+                              void* stream);
+int orl_cache_mark_fresh_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, int64_t now_ticks, uint8_t* d_found,
+                                void* stream);
+int orl_cache_adjust_for_removed_silo_device(orl_ctx* ctx, uint32_t me, uint32_t opts, uint32_t removed_silo,
+                                             uint64_t* d_removed_count, void* stream);
+int orl_cache_peek_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, uint32_t* d_act, uint8_t* d_silo,
+                          int32_t* d_etag, int64_t* d_ttl, int64_t* d_last_refreshed, uint8_t* d_accessed, void* stream);
 
 /* ---- stateless-worker grains (StatelessWorkerDirector, src/OrleansRuntime/Placement/StatelessWorkerDirector.cs:35-80)
  * A [StatelessWorker] grain is never registered in the grain directory (Catalog.cs:1156-1185, singleActivationMode =

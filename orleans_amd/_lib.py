@@ -56,6 +56,8 @@ SW_MAX_LOCAL = 8
 SW_ADDED, SW_DUPLICATE, SW_UNSUPPORTED = 0, 1, 2
 RING_CONSISTENT, RING_VBUCKETS = 0, 1
 CACHE_EVICT_DEVICE, CACHE_EVICT_HOST = 0, 1
+CACHE_NO_ETAG = -1
+TICKS_PER_SECOND = 10_000_000  # .NET ticks (100 ns): the unit of the adaptive cache's timers and clock
 OUTQ_LOOPBACK, OUTQ_PING, OUTQ_SYSTEM, OUTQ_REJECT, OUTQ_OVERFLOW, OUTQ_UNKNOWN_SILO = (
     0xFFFFFFF0, 0xFFFFFFF1, 0xFFFFFFF2, 0xFFFFFFF3, 0xFFFFFFF4, 0xFFFFFFF5)
 DEC_OK, DEC_UNSUPPORTED, DEC_MALFORMED, DEC_UNKNOWN_SILO, DEC_NO_TARGET, DEC_NO_SENDER = 0, 1, 2, 3, 4, 5
@@ -123,6 +125,10 @@ class orl_node_stats(C.Structure):
 class orl_cache_stats(C.Structure):
     _fields_ = [("entries", C.c_uint64), ("tombstones", C.c_uint64), ("evictions", C.c_uint64),
                 ("evict_batches", C.c_uint64), ("rebuilds", C.c_uint64), ("host_fallbacks", C.c_uint64)]
+
+
+class orl_cache_sweep(C.Structure):
+    _fields_ = [("d_keys", C.c_void_p), ("d_etags", C.c_void_p), ("d_owner_offsets", C.c_void_p), ("d_counts", C.c_void_p)]
 
 
 class orl_node_chunk_plan(C.Structure):
@@ -213,6 +219,12 @@ _SIGS = {
     "orl_cache_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "orl_cache_stats": (C.c_int, [_P, _P]),
     "orl_cache_evict_mode": (C.c_int, [_P, C.c_uint32]),
+    "orl_cache_config_adaptive": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_double]),
+    "orl_cache_add_or_update_versioned_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int64, _P]),
+    "orl_cache_maintain_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int64, _P, _P]),
+    "orl_cache_mark_fresh_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P]),
+    "orl_cache_adjust_for_removed_silo_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
+    "orl_cache_peek_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "orl_sw_types_set": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "orl_sw_config": (C.c_int, [_P, C.c_uint64]),
     "orl_sw_add": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),

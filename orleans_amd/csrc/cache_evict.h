@@ -47,14 +47,17 @@ void cache_evict_free(CacheEvictScratch* s);
 // The exact sequential LRU.Add of a batch, stream-ordered (DESIGN "Directory cache: eviction on the device").
 // d_cache_ins: the table the surviving entries are inserted into — d_cache, or the second table when the caller
 // asked for a compaction between the tombstoning and the inserts (`d_rebuild_into` != nullptr, same geometry).
-// d_cnt = {entries, tombstones, error word, cumulative evictions}.
+// d_cnt = {entries, tombstones, error word, cumulative evictions}.  fresh: the adaptive state of the entries the batch
+// leaves (fresh.on == 0: a plain cache).
 int launch_cache_evict_add(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_into, uint64_t* d_cnt, uint64_t capacity,
                            const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
-                           uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s, void* stream);
+                           uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s, void* stream,
+                           const CacheFresh& fresh = CacheFresh{});
 
 // Tombstone compaction alone: the FULL slots of d_src, with their stamps and the generation base, rehashed into d_dst
-// (same geometry, no tombstones); the counters reset to {entries, 0}.
+// (same geometry, no tombstones); the counters reset to {entries, 0}.  adaptive: both tables carry the per-slot adaptive
+// state (orl_internal.h CacheAdaptive), which moves with its entry.
 int launch_cache_rebuild(const DirSlot* d_src, DirSlot* d_dst, uint64_t mask, uint64_t* d_cnt, const CacheEvictScratch& s,
-                         void* stream);
+                         void* stream, bool adaptive = false);
 
 }  // namespace orl

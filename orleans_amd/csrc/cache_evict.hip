@@ -439,12 +439,21 @@ __global__ __launch_bounds__(256) void k_ev_tomb_b(DirSlot* __restrict__ cache, 
 // place, else the first free slot of the chain is claimed by CAS.  Stamp = G + i + 1.
 __global__ __launch_bounds__(256) void k_ev_insert(DirSlot* __restrict__ cache, uint64_t mask, const orl_grain_key* __restrict__ keys,
                                                    const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos, uint32_t n,
-                                                   const uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt) {
+                                                   const uint8_t* __restrict__ keep, uint64_t* __restrict__ cnt, CacheFresh fresh) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || !keep[i]) return;
     const orl_grain_key k = keys[i];
     unsigned long long* gen = gens_of(cache, mask);
     const unsigned long long stamp = gen[mask + 1] + i + 1ull;
+    // adaptive cache: the new GrainDirectoryCacheEntry's state goes where the stamp goes
+    const auto fresh_state = [&](uint64_t slot) {
+        if (!fresh.on) return;
+        const CacheAdaptive a = cache_adaptive(cache, mask);
+        a.etag[slot] = fresh.etags ? fresh.etags[i] : 0;
+        a.ttl[slot] = fresh.initial_ttl;
+        a.last_refreshed[slot] = fresh.now;
+        a.seen[slot] = stamp;
+    };
     const uint64_t w24 = (uint64_t)acts[i] | ((uint64_t)silos[i] << 32) | ((uint64_t)SLOT_FULL << 40);
     const uint64_t start = dir_slot(jenkins3(k.type_code_data, k.n0, k.n1), mask);
     uint64_t cur = start;
@@ -455,6 +464,7 @@ __global__ __launch_bounds__(256) void k_ev_insert(DirSlot* __restrict__ cache, 
             uint64_t* p24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(cache + cur) + 24);
             __hip_atomic_store(p24, w24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             gen[cur] = stamp;
+            fresh_state(cur);
             return;
         }
         cur = (cur + 1) & mask;
@@ -472,6 +482,7 @@ __global__ __launch_bounds__(256) void k_ev_insert(DirSlot* __restrict__ cache, 
                 __hip_atomic_store(kw + 1, k.n0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(kw + 2, k.n1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 gen[cur] = stamp;
+                fresh_state(cur);
                 __atomic_thread_fence(__ATOMIC_RELEASE);  // the key is visible before the slot reads FULL
                 __hip_atomic_store(kw + 3, w24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 add64(&cnt[0], 1);
@@ -494,7 +505,7 @@ __global__ void k_ev_finish(DirSlot* __restrict__ cache, uint64_t mask, uint64_t
 // ---- tombstone compaction -------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_rb_move(const DirSlot* __restrict__ src, DirSlot* __restrict__ dst, uint64_t mask,
-                                                 uint64_t* __restrict__ st, uint64_t* __restrict__ cnt) {
+                                                 uint64_t* __restrict__ st, uint64_t* __restrict__ cnt, uint32_t adaptive) {
     const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     bool moved = false;
     if (s <= mask && src[s].state == SLOT_FULL) {
@@ -511,6 +522,13 @@ __global__ __launch_bounds__(256) void k_rb_move(const DirSlot* __restrict__ src
                 w[2] = e.n1;
                 w[3] = (uint64_t)e.act | ((uint64_t)e.silo << 32) | ((uint64_t)SLOT_FULL << 40);
                 gens_of(dst, mask)[cur] = stamp;
+                if (adaptive) {  // the entry keeps its ETag, timer and access mark (`seen` beside its unchanged stamp)
+                    const CacheAdaptive from = cache_adaptive(src, mask), to = cache_adaptive(dst, mask);
+                    to.etag[cur] = from.etag[s];
+                    to.ttl[cur] = from.ttl[s];
+                    to.last_refreshed[cur] = from.last_refreshed[s];
+                    to.seen[cur] = from.seen[s];
+                }
                 moved = true;
             }
             cur = (cur + 1) & mask;
@@ -592,20 +610,22 @@ void cache_evict_free(CacheEvictScratch* s) {
 }
 
 int launch_cache_rebuild(const DirSlot* d_src, DirSlot* d_dst, uint64_t mask, uint64_t* d_cnt, const CacheEvictScratch& s,
-                         void* stream) {
+                         void* stream, bool adaptive) {
     hipStream_t st = (hipStream_t)stream;
     const uint64_t slots = mask + 1;
     hipError_t e = hipMemsetAsync(d_dst, 0, slots * sizeof(DirSlot) + (slots + 1) * 8, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(k_rb_begin, dim3(1), dim3(64), 0, st, s.st);
-    hipLaunchKernelGGL(k_rb_move, dim3(blocks(slots)), dim3(256), 0, st, d_src, d_dst, mask, s.st, d_cnt);
+    hipLaunchKernelGGL(k_rb_move, dim3(blocks(slots)), dim3(256), 0, st, d_src, d_dst, mask, s.st, d_cnt,
+                       adaptive ? 1u : 0u);
     hipLaunchKernelGGL(k_rb_finish, dim3(1), dim3(64), 0, st, d_src, d_dst, mask, s.st, d_cnt);
     return (int)hipGetLastError();
 }
 
 int launch_cache_evict_add(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_into, uint64_t* d_cnt, uint64_t capacity,
                            const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
-                           uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s, void* stream) {
+                           uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s, void* stream,
+                           const CacheFresh& fresh) {
     hipStream_t st = (hipStream_t)stream;
     const uint64_t slots = mask + 1;
     if (n == 0) return 0;
@@ -652,10 +672,10 @@ int launch_cache_evict_add(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_i
     hipLaunchKernelGGL(k_ev_tomb_b, gn, b, 0, st, d_cache, un, s.nxt_b, s.ev_b, s.old_slot, s.keep, d_cnt);
     DirSlot* into = d_cache;
     if (d_rebuild_into) {
-        if (int r = launch_cache_rebuild(d_cache, d_rebuild_into, mask, d_cnt, s, stream)) return r;
+        if (int r = launch_cache_rebuild(d_cache, d_rebuild_into, mask, d_cnt, s, stream, fresh.on != 0)) return r;
         into = d_rebuild_into;
     }
-    hipLaunchKernelGGL(k_ev_insert, gn, b, 0, st, into, mask, d_keys, d_acts, d_silos, un, s.keep, d_cnt);
+    hipLaunchKernelGGL(k_ev_insert, gn, b, 0, st, into, mask, d_keys, d_acts, d_silos, un, s.keep, d_cnt, fresh);
     hipLaunchKernelGGL(k_ev_finish, dim3(1), dim3(64), 0, st, into, mask, (uint64_t)n, d_cnt, s.st);
     return (int)hipGetLastError();
 }

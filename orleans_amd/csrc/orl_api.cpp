@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "orl_internal.h"
+#include "cache_adaptive.h"
 #include "cache_evict.h"
 
 using namespace orl;
@@ -255,6 +256,12 @@ struct orl_ctx {
     uint64_t cache_slots = 0, cache_ub = 0, cache_tombs_ub = 0;
     uint64_t cache_cap = 0;       // LRU.MaximumSize (orl_cache_config's capacity)
     uint64_t cache_gen_free = 0;  // LRU.generationToFree: the generation of the last entry evicted
+    // adaptive mode (orl_cache_config_adaptive): both tables carry the per-slot state (orl_internal.h CacheAdaptive)
+    bool cache_adaptive = false;
+    int64_t cache_initial_ttl = 0, cache_max_ttl = 0;  // initialExpirationTimer, maxExpirationTimer (.NET ticks)
+    double cache_growth = 0;                           // exponentialTimerGrowth
+    int64_t cache_now = 0;                             // the last now_ticks a call gave (the plain add's DateTime.UtcNow)
+    CacheSweepScratch csw;                             // the maintainer's scratch and output (cache_adaptive.hip)
     // stateless-worker grains (StatelessWorkerDirector.cs:35-80): the listed types with their MaxLocal, and the local
     // catalog's host mirror (SwSlot), uploaded whole when the host changed it (sw_dirty).  orl_sw_set_busy_device makes
     // the device table the newer one (sw_dev_newer): the host calls first read it back (sw_sync_host).  The two flags
@@ -763,7 +770,7 @@ int ensure_staging(orl_ctx* c, size_t in_bytes, size_t out_words) {
 
 void free_device(orl_ctx* c) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
-    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
+    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); cache_sweep_free(&c->csw); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
     f(c->s.pairs_a); f(c->s.pairs_b); f(c->s.idx_a); f(c->s.sorted_keys); f(c->s.tile_hist); f(c->s.tile_cnt); f(c->s.scan_sums); f(c->s.digits); f(c->s.col_sums); f(c->s.col_tot); f(c->s.seg_hist); f(c->s.seg_carry); f(c->s.seg_meta); f(c->s.seg_lb); f(c->s.seg_lbctl); f(c->s.bstart); f(c->s.sstart); f(c->s.gap_q); f(c->s.hot); f(c->s.hot_rows); f(c->s.hot_bmax); f(c->s.pick_word); f(c->s.fan_blk); f(c->s.lsd_hot);
     for (auto& L : c->s.lb) {
         f(L.state);
@@ -2077,8 +2084,8 @@ int orl_stream_queue_batch_device(orl_ctx* c, uint32_t kind, const uint8_t* d_gu
 }
 
 // ---- f4: directory cache ---------------------------------------------------------------------------
-int orl_cache_config(orl_ctx* c, uint64_t capacity) {
-    if (!c) return ORL_E_INVALID;
+namespace {
+int cache_config(orl_ctx* c, uint64_t capacity, bool adaptive) {
     if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
     if (capacity == 0) return fail(c, ORL_E_INVALID, "capacity must be >= 1");
     ORL_HIP(c, hipSetDevice(c->cfg.device));
@@ -2086,14 +2093,19 @@ int orl_cache_config(orl_ctx* c, uint64_t capacity) {
     (void)hipFree(c->d_cache); (void)hipFree(c->d_cache2); (void)hipFree(c->d_cclaim); (void)hipFree(c->d_cstate);
     c->d_cache = nullptr; c->d_cache2 = nullptr; c->d_cclaim = nullptr; c->d_cstate = nullptr;
     cache_evict_free(&c->cev);
+    cache_sweep_free(&c->csw);
     c->cache_slots = 0;
+    c->cache_adaptive = false;
     const uint64_t slots = next_pow2(2 * capacity);
-    // the table, then one u64 LRU generation per slot and the generation base (route_kernels.hip cache_gens)
-    const size_t bytes = slots * sizeof(DirSlot) + (slots + 1) * 8;
+    // the table, then one u64 LRU generation per slot and the generation base (route_kernels.hip cache_gens), then, in
+    // adaptive mode, the per-slot adaptive state (orl_internal.h CacheAdaptive)
+    const size_t bytes = cache_table_bytes(slots, adaptive);
     ORL_HIP(c, hipMalloc((void**)&c->d_cache, bytes));
     ORL_HIP(c, hipMalloc((void**)&c->d_cache2, bytes));
     ORL_HIP(c, hipMemset(c->d_cache2, 0, bytes));
     if (int e = cache_evict_alloc(&c->cev, c->s.max_batch, slots)) return hipfail(c, (hipError_t)e, "cache eviction scratch");
+    if (adaptive)
+        if (int e = cache_sweep_alloc(&c->csw, capacity, slots)) return hipfail(c, (hipError_t)e, "cache sweep scratch");
     ORL_HIP(c, hipMalloc((void**)&c->d_cclaim, slots * 4));
     ORL_HIP(c, hipMalloc((void**)&c->d_cstate, 32));
     ORL_HIP(c, hipMemset(c->d_cache, 0, bytes));
@@ -2104,7 +2116,32 @@ int orl_cache_config(orl_ctx* c, uint64_t capacity) {
     c->cache_gen_free = 0;
     c->cache_ub = c->cache_tombs_ub = 0;
     c->cache_host_evictions = c->cache_evict_batches = c->cache_rebuilds = c->cache_host_fallbacks = 0;
+    c->cache_adaptive = adaptive;
     set_cache_on(c, false);
+    return ORL_OK;
+}
+}  // namespace
+
+int orl_cache_config(orl_ctx* c, uint64_t capacity) {
+    if (!c) return ORL_E_INVALID;
+    return cache_config(c, capacity, false);
+}
+
+int orl_cache_config_adaptive(orl_ctx* c, uint64_t capacity, int64_t initial_ttl_ticks, int64_t max_ttl_ticks, double ttl_growth) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    // what keeps the reference's checked arithmetic from throwing: LastRefreshed.Add(ExpirationTimer) and
+    // ExpirationTimer.Multiply(growth) = checked((long)checked((double)ticks * growth)) (StandardExtensions.cs:34-39)
+    if (initial_ttl_ticks < 0 || initial_ttl_ticks > max_ttl_ticks || max_ttl_ticks > ((int64_t)1 << 61))
+        return fail(c, ORL_E_INVALID, "timers must satisfy 0 <= initial <= max <= 2^61 ticks");
+    if (!std::isfinite(ttl_growth) || ttl_growth < 0 || !((double)max_ttl_ticks * ttl_growth < 9223372036854775808.0))
+        return fail(c, ORL_E_INVALID, "growth must be finite, >= 0 and keep max * growth below 2^63");
+    if (int r = cache_config(c, capacity, true)) return r;
+    c->cache_initial_ttl = initial_ttl_ticks;
+    c->cache_max_ttl = max_ttl_ticks;
+    c->cache_growth = ttl_growth;
+    c->cache_now = 0;
+    c->cache_mode = ORL_CACHE_EVICT_DEVICE;  // the host LRU does not carry the adaptive state
     return ORL_OK;
 }
 
@@ -2209,10 +2246,19 @@ int cache_add_host_lru(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* 
 // and the inserts of an evicting batch, so that even a batch larger than the cache ends with load <= 1/2.  No device-wide
 // sync, no copy to the host.  ORL_CACHE_EVICT_HOST keeps the earlier path (exact counters read back, then the LRU on the
 // host) for A/B runs and as the tests' cross-check.
-int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                                   size_t n, void* stream) {
-    if (!c) return ORL_E_INVALID;
+// On an adaptive cache every entry the batch leaves is a new GrainDirectoryCacheEntry (AdaptiveGrainDirectoryCache.cs:
+// 97-103): d_etags[i] (0 when null), the initial timer, LastRefreshed = the context's `cache_now`, NumAccesses = 0.
+namespace {
+int cache_add(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, const int32_t* d_etags,
+              size_t n, void* stream) {
     if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
+    CacheFresh fresh;
+    if (c->cache_adaptive) {
+        fresh.etags = d_etags;
+        fresh.now = c->cache_now;
+        fresh.initial_ttl = c->cache_initial_ttl;
+        fresh.on = 1;
+    }
     if (n && (!d_keys || !d_acts || !d_silos)) return fail(c, ORL_E_INVALID, "null device buffer");
     if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
     auto fits = [&](uint64_t cnt, uint64_t tombs) {  // no eviction possible, and the table's load stays <= 7/8
@@ -2242,7 +2288,7 @@ int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, cons
             const bool crowded = (c->cache_ub + c->cache_tombs_ub + (evicts ? fresh_ub : n)) * 8 > c->cache_slots * 7;
             if (evicts) {
                 int e = launch_cache_evict_add(c->d_cache, mask, crowded ? c->d_cache2 : nullptr, c->d_cstate, c->cache_cap, d_keys,
-                                               d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st);
+                                               d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st, fresh);
                 if (e) return hipfail(c, (hipError_t)e, "cache eviction launch");
                 ++c->cache_evict_batches;
                 // FULL + TOMB slots grow by at most the new entries (an eviction turns a FULL slot into a tombstone)
@@ -2257,7 +2303,7 @@ int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, cons
                 return ORL_OK;
             }
             // no eviction possible, only tombstones in the way: compact, then the plain update below
-            int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st);
+            int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st, c->cache_adaptive);
             if (e) return hipfail(c, (hipError_t)e, "cache rebuild launch");
             std::swap(c->d_cache, c->d_cache2);
             ++c->cache_rebuilds;
@@ -2265,9 +2311,102 @@ int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, cons
         }
     }
     int e = launch_cache_update(c->d_cache, mask, c->d_cclaim, c->d_cstate, d_keys, d_acts, d_silos, n, c->cfg.n_act,
-                                c->n_silos, c->d_dslot, c->d_dflag, reinterpret_cast<uint32_t*>(c->d_cstate + 2), st, c->d_params);
+                                c->n_silos, c->d_dslot, c->d_dflag, reinterpret_cast<uint32_t*>(c->d_cstate + 2), st, c->d_params,
+                                fresh);
     if (e) return hipfail(c, (hipError_t)e, "cache update launch");
     c->cache_ub += n;
+    return ORL_OK;
+}
+
+// The adaptive calls' common refusals.
+int need_adaptive(orl_ctx* c) {
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!c->cache_slots || !c->cache_adaptive)
+        return fail(c, ORL_E_STATE, "directory cache not configured in adaptive mode (orl_cache_config_adaptive)");
+    return ORL_OK;
+}
+}  // namespace
+
+int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                                   size_t n, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    return cache_add(c, d_keys, d_acts, d_silos, nullptr, n, stream);
+}
+
+int orl_cache_add_or_update_versioned_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                                             const uint8_t* d_silos, const int32_t* d_etags, size_t n, int64_t now_ticks,
+                                             void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_adaptive(c)) return r;
+    if (n && !d_etags) return fail(c, ORL_E_INVALID, "null device buffer");
+    c->cache_now = now_ticks;
+    return cache_add(c, d_keys, d_acts, d_silos, d_etags, n, stream);
+}
+
+// One pass of the maintainer (cache_adaptive.hip).  The host's bounds stay as they are: the pass turns FULL slots into
+// tombstones and nothing else, so the entries only shrink (cache_ub bounds them still) and the occupied slots, FULL +
+// TOMB, do not change (cache_ub + cache_tombs_ub bounds them still) — and the add's path choice reads the bounds only
+// as cache_ub alone and as that sum.
+int orl_cache_maintain_device(orl_ctx* c, uint32_t me, uint32_t opts, int64_t now_ticks, struct orl_cache_sweep* out,
+                              void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_adaptive(c)) return r;
+    if (!out) return fail(c, ORL_E_INVALID, "null result struct");
+    if (me >= c->n_silos) return fail(c, ORL_E_INVALID, "silo %u out of range", me);
+    if (int r = sync_device_state(c)) return r;
+    c->cache_now = now_ticks;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_cache_sweep(c->d_params, c->d_cache, c->cache_slots - 1, c->d_cstate, me,
+                               (opts & ORL_OPT_EXCLUDE_IF_STOPPING) != 0, c->n_silos, now_ticks, c->csw, st);
+    if (e) return hipfail(c, (hipError_t)e, "cache sweep launch");
+    out->d_keys = c->csw.keys;
+    out->d_etags = c->csw.etags;
+    out->d_owner_offsets = c->csw.owner_off;
+    out->d_counts = c->csw.counts;
+    return ORL_OK;
+}
+
+int orl_cache_mark_fresh_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, int64_t now_ticks, uint8_t* d_found,
+                                void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_adaptive(c)) return r;
+    if (n && !d_keys) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    c->cache_now = now_ticks;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_cache_mark_fresh(c->d_cache, c->cache_slots - 1, d_keys, n, now_ticks, c->cache_max_ttl, c->cache_growth, d_found,
+                                    st);
+    if (e) return hipfail(c, (hipError_t)e, "cache mark-fresh launch");
+    return ORL_OK;
+}
+
+int orl_cache_adjust_for_removed_silo_device(orl_ctx* c, uint32_t me, uint32_t opts, uint32_t removed_silo,
+                                             uint64_t* d_removed_count, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
+    if (me >= c->n_silos || removed_silo >= c->n_silos) return fail(c, ORL_E_INVALID, "silo out of range");
+    if (int r = sync_device_state(c)) return r;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_cache_adjust(c->d_params, c->d_cache, c->cache_slots - 1, c->d_cstate, me,
+                                (opts & ORL_OPT_EXCLUDE_IF_STOPPING) != 0, c->n_silos, removed_silo, d_removed_count, st);
+    if (e) return hipfail(c, (hipError_t)e, "cache adjust launch");
+    return ORL_OK;  // the host's bounds stay valid, as after a sweep
+}
+
+int orl_cache_peek_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, uint32_t* d_act, uint8_t* d_silo, int32_t* d_etag,
+                          int64_t* d_ttl, int64_t* d_last_refreshed, uint8_t* d_accessed, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
+    if (!c->cache_adaptive && (d_etag || d_ttl || d_last_refreshed || d_accessed))
+        return fail(c, ORL_E_STATE, "etag, timer, refresh time and access mark exist only in an adaptive cache");
+    if (n && !d_keys) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_cache_peek(c->d_cache, c->cache_slots - 1, c->cache_adaptive, d_keys, n, d_act, d_silo, d_etag, d_ttl,
+                              d_last_refreshed, d_accessed, st);
+    if (e) return hipfail(c, (hipError_t)e, "cache peek launch");
     return ORL_OK;
 }
 
@@ -2305,6 +2444,8 @@ int orl_cache_evict_mode(orl_ctx* c, uint32_t mode) {
     if (!c) return ORL_E_INVALID;
     if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
     if (mode != ORL_CACHE_EVICT_DEVICE && mode != ORL_CACHE_EVICT_HOST) return fail(c, ORL_E_INVALID, "unknown eviction mode %u", mode);
+    if (mode == ORL_CACHE_EVICT_HOST && c->cache_adaptive)
+        return fail(c, ORL_E_STATE, "the host LRU does not carry an adaptive cache's per-entry state");
     c->cache_mode = mode;
     return ORL_OK;
 }

@@ -265,6 +265,40 @@ struct DirView {
     bool lru = false;                     // the cache is populated: lookups stamp its LRU generations (k_route<..., LRU>)
 };
 
+// ---- adaptive directory cache: per-slot state (AdaptiveGrainDirectoryCache.cs:32-70) ----------------
+// An adaptive cache table (orl_cache_config_adaptive) is followed, after its generation array and G, by one ETag,
+// ExpirationTimer and LastRefreshed per slot, and by `seen`: the LRU stamp the slot carried when its NumAccesses was
+// last zero.  A lookup raises the slot's generation (cache_touch) and nothing else, so "accessed since" is
+// generation > seen.  The 8-B arrays come first; a plain cache has none of them.
+struct CacheAdaptive {
+    int64_t* ttl;             // ExpirationTimer, .NET ticks
+    int64_t* last_refreshed;  // LastRefreshed, .NET ticks
+    unsigned long long* seen;
+    int32_t* etag;
+};
+__host__ __device__ inline CacheAdaptive cache_adaptive(const DirSlot* cache, uint64_t mask) {
+    const uint64_t slots = mask + 1;
+    uint8_t* p = reinterpret_cast<uint8_t*>(const_cast<DirSlot*>(cache + slots)) + (slots + 1) * 8;
+    CacheAdaptive a;
+    a.ttl = reinterpret_cast<int64_t*>(p);
+    a.last_refreshed = a.ttl + slots;
+    a.seen = reinterpret_cast<unsigned long long*>(a.last_refreshed + slots);
+    a.etag = reinterpret_cast<int32_t*>(a.seen + slots);
+    return a;
+}
+inline size_t cache_table_bytes(uint64_t slots, bool adaptive) {
+    return slots * sizeof(DirSlot) + (slots + 1) * 8 + (adaptive ? slots * 28 : 0);
+}
+// What a writer of a fresh entry needs beside the entry (a kernel argument): on == 0 is a plain cache.  The entry of
+// batch index i gets etags[i] (0 when etags is null), ttl = initial_ttl, last_refreshed = now, seen = its stamp.
+struct CacheFresh {
+    const int32_t* etags = nullptr;
+    int64_t now = 0;
+    int64_t initial_ttl = 0;
+    uint32_t on = 0;
+    uint32_t pad = 0;
+};
+
 // ---- kernel launchers (route_kernels.hip) ---------------------------------------------------------
 // All return hipError_t as int; they only enqueue on `stream`.
 // KeyExt (string-key) directory slot, 48 B (round 5): the UniqueKey's 24 B, its KeyExt uniform hash, the activation
@@ -390,7 +424,8 @@ int launch_dir_insert(const RouteParams* d_params, DirSlot* d_dir, uint64_t dir_
                       void* stream);
 int launch_cache_update(DirSlot* d_cache, uint64_t mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                         const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act, uint32_t n_silos, uint32_t* d_slot,
-                        uint8_t* d_flag, uint32_t* d_err, void* stream, const RouteParams* d_params);
+                        uint8_t* d_flag, uint32_t* d_err, void* stream, const RouteParams* d_params,
+                        const CacheFresh& fresh = CacheFresh{});
 // The directory cache's LRU generation base (after the cache table and its per-slot generations): += n, on `stream`.
 int launch_cache_gen_advance(const DirSlot* d_cache, uint64_t mask, uint64_t n, void* stream);
 int launch_dir_merge(DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,

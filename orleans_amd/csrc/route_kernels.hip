@@ -4979,12 +4979,20 @@ __global__ __launch_bounds__(256) void k_cache_resolve(const uint32_t* __restric
 __global__ __launch_bounds__(256) void k_cache_commit(DirSlot* __restrict__ cache, uint32_t* __restrict__ claim,
                                                       const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos, uint32_t n,
                                                       const uint32_t* __restrict__ slot_in, const uint8_t* __restrict__ win,
-                                                      uint64_t* __restrict__ cnt, uint64_t mask) {
+                                                      uint64_t* __restrict__ cnt, uint64_t mask, CacheFresh fresh_state) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || !win[i]) return;
     const uint32_t slot = slot_in[i] & kSlotMask;
     unsigned long long* gen = cache_gens(cache, mask);
-    gen[slot] = gen[mask + 1] + i + 1ull;
+    const unsigned long long stamp = gen[mask + 1] + i + 1ull;
+    gen[slot] = stamp;
+    if (fresh_state.on) {  // adaptive cache: a new GrainDirectoryCacheEntry (AdaptiveGrainDirectoryCache.cs:50-58, 97-103)
+        const CacheAdaptive a = cache_adaptive(cache, mask);
+        a.etag[slot] = fresh_state.etags ? fresh_state.etags[i] : 0;
+        a.ttl[slot] = fresh_state.initial_ttl;
+        a.last_refreshed[slot] = fresh_state.now;
+        a.seen[slot] = stamp;
+    }
     const bool fresh = cache[slot].state == SLOT_CLAIMED;  // a new entry (else an update of a FULL one)
     uint64_t* w24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(cache + slot) + 24);
     *w24 = (uint64_t)acts[i] | ((uint64_t)silos[i] << 32) | ((uint64_t)SLOT_FULL << 40);
@@ -6364,14 +6372,15 @@ int launch_dir_merge(DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint6
 
 int launch_cache_update(DirSlot* d_cache, uint64_t mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                         const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act, uint32_t n_silos, uint32_t* d_slot,
-                        uint8_t* d_flag, uint32_t* d_err, void* stream, const RouteParams* d_params) {
+                        uint8_t* d_flag, uint32_t* d_err, void* stream, const RouteParams* d_params, const CacheFresh& fresh) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return 0;
     const dim3 g(ceil_div(n, 256)), b(256);
     hipLaunchKernelGGL(k_cache_probe, g, b, 0, st, d_cache, mask, d_claim, d_keys, d_acts, d_silos, (uint32_t)n, n_act, n_silos,
                        d_params->local, d_slot, d_err);
     hipLaunchKernelGGL(k_cache_resolve, g, b, 0, st, d_claim, (uint32_t)n, d_slot, d_flag);
-    hipLaunchKernelGGL(k_cache_commit, g, b, 0, st, d_cache, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_flag, d_cnt, mask);
+    hipLaunchKernelGGL(k_cache_commit, g, b, 0, st, d_cache, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_flag, d_cnt, mask,
+                       fresh);
     return launch_cache_gen_advance(d_cache, mask, n, stream);
 }
 

@@ -570,6 +570,67 @@ class GrainDirectoryEngine:
         L.CACHE_EVICT_HOST (the exact LRU on the host over the table read back: for A/B runs and cross-checks)."""
         self._ck(self._lib.orl_cache_evict_mode(self._ctx, int(mode)))
 
+    # ---- adaptive directory cache (DESIGN §12): ETags, timers and the maintainer on the device ----
+    def cache_config_adaptive(self, capacity: int, initial_ttl_ticks: int = 30 * L.TICKS_PER_SECOND,
+                              max_ttl_ticks: int = 240 * L.TICKS_PER_SECOND, ttl_growth: float = 2.0) -> None:
+        """cache_config plus AdaptiveGrainDirectoryCache's per-entry state; the defaults are the reference's
+        (GlobalConfiguration.cs:413-417, with capacity 1,000,000).  Times are .NET ticks; the caller supplies `now`."""
+        self._ck(self._lib.orl_cache_config_adaptive(self._ctx, int(capacity), int(initial_ttl_ticks), int(max_ttl_ticks),
+                                                     float(ttl_growth)))
+
+    def cache_add_or_update_versioned_device(self, d_keys, d_acts, d_silos, d_etags, n: int, now_ticks: int,
+                                             stream=None) -> None:
+        """AddOrUpdate(key, value, version) (AdaptiveGrainDirectoryCache.cs:97-103) per entry in batch order."""
+        self._ck(self._lib.orl_cache_add_or_update_versioned_device(self._ctx, ptr(d_keys), ptr(d_acts), ptr(d_silos),
+                                                                    ptr(d_etags), int(n), int(now_ticks), ptr(stream)))
+
+    def cache_maintain_device(self, me: int, now_ticks: int, opts: int = L.OPT_EXCLUDE_IF_STOPPING, stream=None):
+        """One pass of AdaptiveDirectoryCacheMaintainer.Run (:54-143) on `stream`.  Returns the L.orl_cache_sweep of device
+        pointers (valid until the next sweep): d_keys / d_etags owner-major, d_owner_offsets[n_silos + 1], d_counts[5]."""
+        out = L.orl_cache_sweep()
+        self._ck(self._lib.orl_cache_maintain_device(self._ctx, int(me), int(opts), int(now_ticks), C.byref(out), ptr(stream)))
+        return out
+
+    def cache_maintain(self, me: int, now_ticks: int, opts: int = L.OPT_EXCLUDE_IF_STOPPING, stream=None) -> dict:
+        """cache_maintain_device, then a device synchronise and the results as numpy arrays: keys (KEY_DTYPE), etags
+        (int32), owner_offsets (uint32, n_silos + 1) and counts = {self_owned, kept, expired, refresh, owner_null}."""
+        sw = self.cache_maintain_device(me, now_ticks, opts, stream)
+        counts = self._from_device(sw.d_counts, 5, np.uint64)
+        off = self._from_device(sw.d_owner_offsets, self.n_silos + 1, np.uint32)
+        n = int(off[-1])
+        return {"keys": self._from_device(sw.d_keys, n, L.KEY_DTYPE), "etags": self._from_device(sw.d_etags, n, np.int32),
+                "owner_offsets": off,
+                "counts": dict(zip(("self_owned", "kept", "expired", "refresh", "owner_null"), (int(x) for x in counts)))}
+
+    def cache_mark_fresh_device(self, d_keys, n: int, now_ticks: int, d_found=None, stream=None) -> None:
+        """MarkAsFresh (AdaptiveGrainDirectoryCache.cs:150-159) per key; the keys of a batch must be distinct."""
+        self._ck(self._lib.orl_cache_mark_fresh_device(self._ctx, ptr(d_keys), int(n), int(now_ticks), ptr(d_found), ptr(stream)))
+
+    def cache_adjust_for_removed_silo_device(self, me: int, removed_silo: int, d_removed_count=None,
+                                             opts: int = L.OPT_EXCLUDE_IF_STOPPING, stream=None) -> None:
+        """LocalGrainDirectory.AdjustLocalCache (:330-344); call it after remove_server.  Any cache, adaptive or plain."""
+        self._ck(self._lib.orl_cache_adjust_for_removed_silo_device(self._ctx, int(me), int(opts), int(removed_silo),
+                                                                    ptr(d_removed_count), ptr(stream)))
+
+    def cache_peek_device(self, d_keys, n: int, d_act=None, d_silo=None, d_etag=None, d_ttl=None, d_last_refreshed=None,
+                          d_accessed=None, stream=None) -> None:
+        """The entries of n keys without an LRU stamp and without an access; a miss gives act NO_ACT.  Every output is
+        optional; the last four need an adaptive cache."""
+        self._ck(self._lib.orl_cache_peek_device(self._ctx, ptr(d_keys), int(n), ptr(d_act), ptr(d_silo), ptr(d_etag),
+                                                 ptr(d_ttl), ptr(d_last_refreshed), ptr(d_accessed), ptr(stream)))
+
+    def _from_device(self, d_ptr, n: int, dtype) -> np.ndarray:
+        """n elements of a device buffer the library owns, after a device synchronise (the HIP runtime the library is
+        linked against, reached through the library's own handle)."""
+        out = np.zeros(n, dtype)
+        sync, copy = self._lib.hipDeviceSynchronize, self._lib.hipMemcpy
+        sync.restype, sync.argtypes = C.c_int, []
+        copy.restype, copy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = sync() or (copy(ptr(out), C.c_void_p(d_ptr), out.nbytes, 2) if out.nbytes else 0)  # 2 = hipMemcpyDeviceToHost
+        if rc:
+            raise OrleansRouteError(L.E_DEVICE, f"HIP error {rc} reading a device buffer")
+        return out
+
     # ---- stateless-worker grains (StatelessWorkerDirector.cs:35-80) ----
     def set_stateless_types(self, type_code_data: Sequence[int], max_local: Sequence[int]) -> None:
         """The [StatelessWorker] grain types with their MaxLocal (orl_sw_types_set; GrainTypeData.cs:43-50,115,
