@@ -808,7 +808,10 @@ int orl_ctx_create(const orl_config* cfg, orl_ctx** out) {
     c->hp.mem_tcd = (uint64_t)ORL_CAT_SYSTEM_GRAIN << 56;
     c->hp.mem_n0 = 0x11E0C21E01145FECull;
     c->hp.mem_n1 = 0x9B012447FBD00591ull;
-    const uint64_t slots = next_pow2(std::max<uint64_t>(cfg->dir_capacity, 1) * 2);
+    // next_pow2(2 * dir_capacity) slots as orleans_route.h documents, without next_pow2()'s 16-slot floor: a partition
+    // for one entry is two slots (the probe walks, the claim protocol and the 7/8 rule hold from two slots up)
+    uint64_t slots = 2;
+    while (slots < std::max<uint64_t>(cfg->dir_capacity, 1) * 2) slots <<= 1;
     try {
         c->table.assign(slots, DirSlot{});
     } catch (...) {
@@ -1969,8 +1972,7 @@ int orl_dir_split_device(orl_ctx* c, uint32_t me, uint32_t flags, orl_grain_key*
 
 int orl_dir_compact(orl_ctx* c) {
     if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return ORL_OK;
-    if (int r = ensure_mirror(c)) return r;
+    if (int r = ensure_mirror(c)) return r;  // a host-only context's mirror is never stale
     if (c->tombs == 0) return ORL_OK;
     std::vector<DirSlot> old;
     old.swap(c->table);
@@ -1984,7 +1986,9 @@ int orl_dir_compact(orl_ctx* c) {
         ++c->count;
     }
     c->dir_dirty = true;
-    return sync_device_state(c);
+    // a host-only context (device < 0) has only the mirror: its host registrations count tombstones against the load
+    // too, so without this rebuild a half-loaded mirror with tombstones could never take a registration again
+    return c->device_mode ? sync_device_state(c) : ORL_OK;
 }
 
 // ---- f3: stream / reminder rings -----------------------------------------------------------------
