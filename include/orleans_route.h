@@ -246,6 +246,67 @@ int orl_dir_count(const orl_ctx* ctx, uint64_t* n_out);
 /* Host lookup (LookUpGrain without the IsValidSilo filter): act/silo or ORL_NO_ACT/ORL_NULL_SILO */
 int orl_dir_lookup_host(const orl_ctx* ctx, const orl_grain_key* keys, size_t n, uint32_t* act, uint8_t* silo);
 
+/* ---- version tags and LookUpMany (the owner's side of the directory cache's refresh) -------------------
+ * GrainInfo.VersionTag (GrainDirectoryPartition.cs:57-184): 0 at construction, rand.Next() on every change.  The draw is
+ * the caller's (as ActivationId.NewId and SafeRandom are): the library stores and compares it, so parity with
+ * the reference stays exact.  Tags are >= 0, the range of Random.Next(); ORL_DIR_NO_ETAG (-1, GrainInfo.NO_ETAG) means
+ * "absent".  One int32 per partition slot, beside the table, on the device and in the host mirror; the KeyExt table is not
+ * covered.
+ * orl_dir_versions_enable: allocates the tags; entries already present get 0.  Idempotent; works on a host-only context.
+ *   A context that never calls it runs exactly as before.  Every versioned call below needs it (ORL_E_STATE otherwise).
+ *   On a versioned partition the unversioned calls (orl_dir_insert_single, its _device form, orl_dir_merge_device)
+ *   behave as if every tag and draw were 0.  A removed grain's tag is dead: whoever registers the grain next writes its
+ *   own (orl_dir_remove*, orl_dir_split_device with ORL_SPLIT_REMOVE; split output carries no tags, the receiver registers
+ *   with fresh draws).  orl_dir_compact moves tags with their entries.
+ * orl_dir_insert_single_versioned[_device]: orl_dir_insert_single[_device] with tags[i] = message i's draw, stored only
+ *   when message i inserts (AddSingleActivation returns the tag, :270-287).  winner_tag[i] (optional) = the grain's
+ *   VersionTag after the call: the caller's own for ORL_INS_INSERTED, the winner's for ORL_INS_EXISTING (an earlier message
+ *   of the batch or an entry from before), ORL_DIR_NO_ETAG for every other status.  A negative tag: the host call fails
+ *   with ORL_E_INVALID before applying anything; the device call gives that message ORL_INS_UNSUPPORTED.
+ * orl_dir_merge_versioned_device: orl_dir_merge_device with d_tags[i] = the incoming copy's VersionTag and d_draws[i] = a
+ *   draw (GrainDirectoryPartition.Merge :366-383, GrainInfo.Merge :146-183).  ORL_MERGE_INSERTED stores the incoming tag
+ *   (the GrainInfo is added as is); ORL_MERGE_KEPT and ORL_MERGE_REPLACED store the draw (Merge added an instance, so the
+ *   entry was modified whichever activation survives); SAME, DUPLICATE and UNSUPPORTED leave the tag alone.  A negative
+ *   tag or draw gives ORL_MERGE_UNSUPPORTED.
+ * orl_dir_lookup_many_device / _host: RemoteGrainDirectory.LookUpMany (RemoteGrainDirectory.cs:349-380) for n
+ *   (grain, etag) requests, in request order, with curGen = GetGrainETag(grain) (:346-359):
+ *     ORL_LUM_UNCHANGED      present, curGen == etags[i]               etag_out = curGen, act / silo = ORL_NO_ACT / ORL_NULL_SILO
+ *     ORL_LUM_ABSENT         not in the partition                      etag_out = -1, none
+ *     ORL_LUM_UPDATED        present, curGen != etags[i], the activation's silo functional: etag_out = curGen, the entry
+ *     ORL_LUM_UPDATED_EMPTY  present, curGen != etags[i], silo not functional (LookUpGrain's IsValidSilo filter leaves a
+ *                            non-null empty list with the tag, :326-344): etag_out = curGen, none
+ *     ORL_LUM_UNSUPPORTED    KeyExt or SystemTarget key (not held in this table: host path)   etag_out = -1, none
+ *   No ownership check (LookUpMany makes none): the ring plays no part, only functional[].  A request etag of -1 against a
+ *   present entry gives UPDATED.  A key may repeat.  d_counts (optional, device u64[5]) is written, not accumulated, with
+ *   the number of requests of each kind.  The device form runs on the caller's stream without a device-wide sync or a
+ *   copy to the host, needs no scratch (n is not limited by max_batch) and sees the partition as of its position in the
+ *   stream (host-side changes are uploaded first).  The host form reads the mirror (downloaded first when device calls
+ *   changed the partition).
+ * The refresh loop, device to device: the requester's orl_cache_maintain_device lists, per owner o, d_keys + off[o] and
+ *   d_etags + off[o]; in one process those pointers go unchanged to the owner context's orl_dir_lookup_many_device; the
+ *   response is applied at the requester in maximal runs of one kind (further below). */
+#define ORL_DIR_NO_ETAG (-1)
+#define ORL_LUM_UNCHANGED 0u
+#define ORL_LUM_ABSENT 1u
+#define ORL_LUM_UPDATED 2u
+#define ORL_LUM_UPDATED_EMPTY 3u
+#define ORL_LUM_UNSUPPORTED 4u
+int orl_dir_versions_enable(orl_ctx* ctx);
+int orl_dir_insert_single_versioned(orl_ctx* ctx, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos,
+                                    const int32_t* tags, size_t n, uint32_t* winner_act, uint8_t* winner_silo,
+                                    int32_t* winner_tag, uint8_t* status);
+int orl_dir_insert_single_versioned_device(orl_ctx* ctx, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                                           const uint8_t* d_silos, const int32_t* d_tags, size_t n, uint32_t* d_winner_act,
+                                           uint8_t* d_winner_silo, int32_t* d_winner_tag, uint8_t* d_status, void* stream);
+int orl_dir_merge_versioned_device(orl_ctx* ctx, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                                   const int32_t* d_tags, const int32_t* d_draws, size_t n, const orl_grain_key* d_act_keys,
+                                   uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act, uint8_t* d_dropped_silo,
+                                   void* stream);
+int orl_dir_lookup_many_device(orl_ctx* ctx, const orl_grain_key* d_keys, const int32_t* d_etags, size_t n, uint8_t* d_kind,
+                               int32_t* d_etag_out, uint32_t* d_act, uint8_t* d_silo, uint64_t* d_counts, void* stream);
+int orl_dir_lookup_many_host(orl_ctx* ctx, const orl_grain_key* keys, const int32_t* etags, size_t n, uint8_t* kind,
+                             int32_t* etag_out, uint32_t* act, uint8_t* silo);
+
 /* ---- stage 1 alone (tests) ---------------------------------------------------------------- */
 int orl_hash_batch(orl_ctx* ctx, const orl_grain_key* keys, size_t n, uint32_t* hashes_out);
 
@@ -480,8 +541,19 @@ int orl_cache_evict_mode(orl_ctx* ctx, uint32_t mode);
  * ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) on the host: split the owner's response into
  * maximal runs of one kind and issue them in order — an activation list returned: orl_cache_add_or_update_versioned_device
  * with the returned etag; etag -1 and no list: orl_cache_remove_device; an etag only: orl_cache_mark_fresh_device.  That is
- * the reference's sequential loop.  The owner's side of the exchange (RemoteGrainDirectory.LookUpMany) needs a version tag
- * per directory entry, which the partition table does not hold: it stays with the host. */
+ * the reference's sequential loop.
+ *
+ * The whole refresh, device to device:
+ *   1. requester: orl_cache_maintain_device → per owner o the lists d_keys + off[o], d_etags + off[o] (device pointers);
+ *   2. owner o (a context with orl_dir_versions_enable): orl_dir_lookup_many_device on those pointers, unchanged when
+ *      both contexts live in one process → per request a kind, the current tag and, for ORL_LUM_UPDATED, the activation;
+ *   3. requester, per maximal run of one kind in request order: ORL_LUM_UPDATED → orl_cache_add_or_update_versioned_device
+ *      with the returned activation and tag; ORL_LUM_ABSENT and ORL_LUM_UNSUPPORTED → orl_cache_remove_device;
+ *      ORL_LUM_UNCHANGED → orl_cache_mark_fresh_device.
+ * ORL_LUM_UPDATED_EMPTY (the entry exists but its only activation sits on a silo that is not functional) is an empty
+ * activation list with a tag in the reference, which the requester's AddOrUpdate would cache as such.  The device cache
+ * holds one activation per grain and no empty lists, so the requester removes the entry (orl_cache_remove_device): the
+ * next lookup misses either way, but the requester's entry count and LRU state differ from the reference's there. */
 #define ORL_CACHE_NO_ETAG (-1) /* GrainInfo.NO_ETAG */
 struct orl_cache_sweep {
     const orl_grain_key* d_keys;      /* the refresh lists, owner-major */

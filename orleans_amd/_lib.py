@@ -65,6 +65,8 @@ SENDER_FROM_HEADER = 0xFF
 STAMP_OK, STAMP_COMPLETE, STAMP_SKIPPED, STAMP_UNSUPPORTED, STAMP_MALFORMED, STAMP_OVERFLOW = 0, 1, 2, 3, 4, 5
 STAMP_MAX_GROWTH = 72
 MERGE_INSERTED, MERGE_KEPT, MERGE_REPLACED, MERGE_SAME, MERGE_DUPLICATE, MERGE_UNSUPPORTED = 0, 1, 2, 3, 4, 5
+DIR_NO_ETAG = -1  # GrainInfo.NO_ETAG: no entry (version tags are >= 0)
+LUM_UNCHANGED, LUM_ABSENT, LUM_UPDATED, LUM_UPDATED_EMPTY, LUM_UNSUPPORTED = 0, 1, 2, 3, 4  # orl_dir_lookup_many_* kinds
 
 Q_PROBE_FORM, Q_FULL_UPLOADS, Q_SLOT_PATCHES, Q_DEVICE, Q_N_ACT, Q_MAX_BATCH, Q_RANK_MODE = 1, 2, 3, 4, 5, 6, 7
 Q_WIRE_DIGEST = 8
@@ -168,6 +170,12 @@ _SIGS = {
     "orl_route_keyext_device": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     "orl_dir_count": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "orl_dir_lookup_host": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "orl_dir_versions_enable": (C.c_int, [_P]),
+    "orl_dir_insert_single_versioned": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "orl_dir_insert_single_versioned_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "orl_dir_merge_versioned_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, C.c_uint32, _P, _P, _P, _P]),
+    "orl_dir_lookup_many_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "orl_dir_lookup_many_host": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
     "orl_hash_batch": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "orl_route_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P]),
     "orl_route_batch_narrow": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, _P, _P, _P]),

@@ -19,6 +19,7 @@
 
 #include "orl_internal.h"
 #include "cache_adaptive.h"
+#include "dir_versions.h"
 #include "cache_evict.h"
 
 using namespace orl;
@@ -214,6 +215,11 @@ struct orl_ctx {
     std::vector<uint64_t> h_csr_off;
     bool mirror_stale = false;       // device mutations since the mirror was last downloaded
     uint64_t count_ub = 0, tombs_ub = 0;  // upper bounds while the mirror is stale (capacity checks without a sync)
+    // version tags (orl_dir_versions_enable; GrainInfo.VersionTag): one int32 per slot beside the mirror and beside the
+    // device table; they follow the slots through the upload, the slot patches, the mirror download and the compaction
+    bool versions = false;
+    std::vector<int32_t> vtag;
+    int32_t* d_vtag = nullptr;
     // device state
     DirSlot* d_table = nullptr;
     ProbeSlot* d_probe = nullptr;    // compact probe table of d_table (ProbeSlot, orl_internal.h)
@@ -521,7 +527,8 @@ int patch_dirty_slots(orl_ctx* c) {
     if (c->hp.n_probe_types != 1) p8 = false;
     c->probe8_valid = p8;
     if (rebuild16) p16 = false;
-    const size_t bytes = m * (sizeof(DirSlot) + sizeof(ProbeSlot) + sizeof(uint2) + 4);
+    const size_t idx_off = m * (sizeof(DirSlot) + sizeof(ProbeSlot) + sizeof(uint2));
+    const size_t bytes = idx_off + m * 4 + (c->versions ? m * 4 : 0);  // the slots' tags follow the indices
     if (bytes > c->patch_cap) {
         if (c->d_patch_data) (void)hipFree(c->d_patch_data);
         c->d_patch_data = nullptr;
@@ -543,6 +550,7 @@ int patch_dirty_slots(orl_ctx* c) {
         h16[k] = probe16_of(d, t);
         h8[k] = probe8_of(d);
         hi[k] = c->dirty_slots[k];
+        if (c->versions) hi[m + k] = (uint32_t)c->vtag[c->dirty_slots[k]];
     }
     uint8_t* dd = static_cast<uint8_t*>(c->d_patch_data);
     ORL_HIP(c, hipMemcpy(dd, h.data(), bytes, hipMemcpyHostToDevice));
@@ -551,6 +559,11 @@ int patch_dirty_slots(orl_ctx* c) {
                              reinterpret_cast<const uint2*>(dd + m * (sizeof(DirSlot) + sizeof(ProbeSlot))), (uint32_t)m,
                              c->d_table, p16 ? c->d_probe : nullptr, p8 ? c->d_probe8 : nullptr, c->stream);
     if (e) return hipfail(c, (hipError_t)e, "directory patch launch");
+    if (c->versions) {
+        e = launch_tag_patch(reinterpret_cast<const uint32_t*>(dd + idx_off), reinterpret_cast<const int32_t*>(dd + idx_off + m * 4),
+                             (uint32_t)m, c->d_vtag, c->stream);
+        if (e) return hipfail(c, (hipError_t)e, "version tag patch launch");
+    }
     ORL_HIP(c, hipStreamSynchronize(c->stream));
     const uint64_t st[3] = {c->count, c->tombs, 0};
     ORL_HIP(c, hipMemcpy(c->d_dirstate, st, sizeof st, hipMemcpyHostToDevice));
@@ -631,6 +644,8 @@ int sync_device_state(orl_ctx* c) {
             ORL_HIP(c, hipMemset(c->d_table, 0, c->table.size() * sizeof(DirSlot)));
         else
             ORL_HIP(c, hipMemcpy(c->d_table, c->table.data(), c->table.size() * sizeof(DirSlot), hipMemcpyHostToDevice));
+        if (c->versions)
+            ORL_HIP(c, hipMemcpy(c->d_vtag, c->vtag.data(), c->vtag.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         const uint64_t st[3] = {c->count, c->tombs, 0};
         ORL_HIP(c, hipMemcpy(c->d_dirstate, st, sizeof st, hipMemcpyHostToDevice));
         c->dir_dirty = false;
@@ -721,6 +736,8 @@ int ensure_mirror(orl_ctx* c) {
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     ORL_HIP(c, hipDeviceSynchronize());
     ORL_HIP(c, hipMemcpy(c->table.data(), c->d_table, c->table.size() * sizeof(DirSlot), hipMemcpyDeviceToHost));
+    if (c->versions)
+        ORL_HIP(c, hipMemcpy(c->vtag.data(), c->d_vtag, c->vtag.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     uint64_t full = 0, tomb = 0;
     for (const DirSlot& d : c->table) {
         full += d.state == SLOT_FULL;
@@ -770,7 +787,7 @@ int ensure_staging(orl_ctx* c, size_t in_bytes, size_t out_words) {
 
 void free_device(orl_ctx* c) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
-    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); cache_sweep_free(&c->csw); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
+    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_vtag); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); cache_sweep_free(&c->csw); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
     f(c->s.pairs_a); f(c->s.pairs_b); f(c->s.idx_a); f(c->s.sorted_keys); f(c->s.tile_hist); f(c->s.tile_cnt); f(c->s.scan_sums); f(c->s.digits); f(c->s.col_sums); f(c->s.col_tot); f(c->s.seg_hist); f(c->s.seg_carry); f(c->s.seg_meta); f(c->s.seg_lb); f(c->s.seg_lbctl); f(c->s.bstart); f(c->s.sstart); f(c->s.gap_q); f(c->s.hot); f(c->s.hot_rows); f(c->s.hot_bmax); f(c->s.pick_word); f(c->s.fan_blk); f(c->s.lsd_hot);
     for (auto& L : c->s.lb) {
         f(L.state);
@@ -1354,14 +1371,20 @@ int orl_dir_insert_keyext_device(orl_ctx* c, const orl_grain_key* d_keys, const 
     return ORL_OK;
 }
 
-int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n,
-                          uint32_t* wact, uint8_t* wsilo, uint8_t* status) {
-    if (!c || (n && (!keys || !acts || !silos))) return ORL_E_INVALID;
+}  // extern "C"
+
+namespace {
+
+// orl_dir_insert_single and its versioned form: tags == nullptr is the unversioned call (every draw 0 on a versioned
+// partition); wtag is written only by the versioned call.
+int dir_insert_host(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const int32_t* tags,
+                    size_t n, uint32_t* wact, uint8_t* wsilo, int32_t* wtag, uint8_t* status) {
     if (int r = ensure_mirror(c)) return r;
     for (size_t i = 0; i < n; ++i) {
         uint8_t st;
         uint32_t a = ORL_NO_ACT;
         uint8_t s = ORL_NULL_SILO;
+        int32_t wt = ORL_DIR_NO_ETAG;
         const orl_grain_key& k = keys[i];
         const uint32_t cat = (uint32_t)(k.type_code_data >> 56);
         if (acts[i] >= c->cfg.n_act) return fail(c, ORL_E_INVALID, "act %u >= n_act %u at %zu", acts[i], c->cfg.n_act, i);
@@ -1380,6 +1403,7 @@ int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t*
                     st = ORL_INS_EXISTING;
                     a = c->table[at].act;
                     s = c->table[at].silo;
+                    if (c->versions) wt = c->vtag[at];
                 } else {
                     if (fr < 0 || (c->count + c->tombs + 1) * 2 > c->table.size())
                         return fail(c, ORL_E_CAPACITY, "directory full (%llu entries)", (unsigned long long)c->count);
@@ -1388,6 +1412,7 @@ int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t*
                     d.tcd = k.type_code_data; d.n0 = k.n0; d.n1 = k.n1;
                     d.act = acts[i]; d.silo = silos[i]; d.state = SLOT_FULL; d.pad = 0;
                     ++c->count;
+                    if (c->versions) c->vtag[fr] = wt = tags ? tags[i] : 0;  // VersionTag = rand.Next() (:111)
                     mark_slot(c, (uint64_t)fr);
                     st = ORL_INS_INSERTED;
                     a = acts[i];
@@ -1398,6 +1423,87 @@ int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t*
         if (status) status[i] = st;
         if (wact) wact[i] = a;
         if (wsilo) wsilo[i] = s;
+        if (wtag) wtag[i] = wt;
+    }
+    return ORL_OK;
+}
+
+int need_versions(orl_ctx* c, bool device = false) {
+    if (device && !c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    return c->versions ? ORL_OK : fail(c, ORL_E_STATE, "version tags are not enabled (orl_dir_versions_enable)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n,
+                          uint32_t* wact, uint8_t* wsilo, uint8_t* status) {
+    if (!c || (n && (!keys || !acts || !silos))) return ORL_E_INVALID;
+    return dir_insert_host(c, keys, acts, silos, nullptr, n, wact, wsilo, nullptr, status);
+}
+
+int orl_dir_versions_enable(orl_ctx* c) {
+    if (!c) return ORL_E_INVALID;
+    if (c->versions) return ORL_OK;
+    if (c->device_mode) {
+        // entries already present, on the device or in the mirror, get GrainInfo()'s VersionTag = 0
+        ORL_HIP(c, hipSetDevice(c->cfg.device));
+        ORL_HIP(c, hipDeviceSynchronize());
+        ORL_HIP(c, hipMalloc((void**)&c->d_vtag, c->table.size() * sizeof(int32_t)));
+        ORL_HIP(c, hipMemset(c->d_vtag, 0, c->table.size() * sizeof(int32_t)));
+        ORL_HIP(c, hipDeviceSynchronize());
+    }
+    c->vtag.assign(c->table.size(), 0);
+    c->versions = true;
+    return ORL_OK;
+}
+
+int orl_dir_insert_single_versioned(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos,
+                                    const int32_t* tags, size_t n, uint32_t* wact, uint8_t* wsilo, int32_t* wtag,
+                                    uint8_t* status) {
+    if (!c || (n && (!keys || !acts || !silos || !tags))) return ORL_E_INVALID;
+    if (int r = need_versions(c)) return r;
+    for (size_t i = 0; i < n; ++i)  // Random.Next() is never negative; -1 is "absent"
+        if (tags[i] < 0) return fail(c, ORL_E_INVALID, "version tag %d < 0 at %zu", tags[i], i);
+    return dir_insert_host(c, keys, acts, silos, tags, n, wact, wsilo, wtag, status);
+}
+
+int orl_dir_lookup_many_host(orl_ctx* c, const orl_grain_key* keys, const int32_t* etags, size_t n, uint8_t* kind,
+                             int32_t* etag_out, uint32_t* act, uint8_t* silo) {
+    if (!c || (n && (!keys || !etags || !kind || !etag_out || !act || !silo))) return ORL_E_INVALID;
+    if (int r = need_versions(c)) return r;
+    if (int r = ensure_mirror(c)) return r;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t cat = (uint32_t)(keys[i].type_code_data >> 56);
+        uint8_t kd;
+        int32_t cur = ORL_DIR_NO_ETAG;
+        uint32_t a = ORL_NO_ACT;
+        uint8_t s = ORL_NULL_SILO;
+        if (cat == ORL_CAT_KEYEXT_GRAIN || cat == ORL_CAT_SYSTEM_TARGET) {
+            kd = ORL_LUM_UNSUPPORTED;
+        } else {
+            const int64_t at = dir_find(c, keys[i], nullptr);
+            if (at < 0) {
+                kd = ORL_LUM_ABSENT;
+            } else {
+                const DirSlot& d = c->table[at];
+                cur = c->vtag[at];  // GetGrainETag
+                if (cur == etags[i]) {
+                    kd = ORL_LUM_UNCHANGED;
+                } else if (d.silo < c->n_silos && c->functional[d.silo]) {  // LookUpGrain's IsValidSilo filter
+                    kd = ORL_LUM_UPDATED;
+                    a = d.act;
+                    s = d.silo;
+                } else {
+                    kd = ORL_LUM_UPDATED_EMPTY;
+                }
+            }
+        }
+        kind[i] = kd;
+        etag_out[i] = cur;
+        act[i] = a;
+        silo[i] = s;
     }
     return ORL_OK;
 }
@@ -1875,10 +1981,26 @@ int orl_wire_types_set(orl_ctx* c, uint32_t n, const uint64_t* tcd) {
     return ORL_OK;
 }
 
-int orl_dir_insert_single_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                                 size_t n, uint32_t* d_wact, uint8_t* d_wsilo, uint8_t* d_status, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!d_keys || !d_acts || !d_silos || !d_status)) return fail(c, ORL_E_INVALID, "null device buffer");
+}  // extern "C"
+
+namespace {
+
+// The tags a device registration or merge kernel sees: none on a partition without versions; d_in / d_draws == nullptr
+// are the unversioned calls on a versioned partition (zeros).
+DirTags dir_tags(const orl_ctx* c, const int32_t* d_in, const int32_t* d_draws, int32_t* d_winner) {
+    DirTags vt;
+    if (c->versions) {
+        vt.slot = c->d_vtag;
+        vt.in = d_in;
+        vt.draws = d_draws;
+        vt.winner = d_winner;
+    }
+    return vt;
+}
+
+int dir_insert_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                      const int32_t* d_tags, size_t n, uint32_t* d_wact, uint8_t* d_wsilo, int32_t* d_wtag, uint8_t* d_status,
+                      void* stream) {
     if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
@@ -1896,7 +2018,7 @@ int orl_dir_insert_single_device(orl_ctx* c, const orl_grain_key* d_keys, const 
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int e = launch_dir_insert(c->d_params, c->d_table, c->mask, c->d_claim, c->d_dirstate, d_keys, d_acts, d_silos, n,
                               c->cfg.n_act, c->n_silos, c->d_dslot, d_wact, d_wsilo, d_status,
-                              reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st);
+                              reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st, dir_tags(c, d_tags, nullptr, d_wtag));
     if (e) return hipfail(c, (hipError_t)e, "directory insert launch");
     c->count_ub += n;
     c->mirror_stale = true;
@@ -1904,11 +2026,9 @@ int orl_dir_insert_single_device(orl_ctx* c, const orl_grain_key* d_keys, const 
     return ORL_OK;
 }
 
-int orl_dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
-                         const orl_grain_key* d_act_keys, uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act,
-                         uint8_t* d_dropped_silo, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!d_keys || !d_acts || !d_silos || !d_status || !d_act_keys)) return fail(c, ORL_E_INVALID, "null device buffer");
+int dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                     const int32_t* d_tags, const int32_t* d_draws, size_t n, const orl_grain_key* d_act_keys,
+                     uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act, uint8_t* d_dropped_silo, void* stream) {
     if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
@@ -1925,11 +2045,66 @@ int orl_dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     int e = launch_dir_merge(c->d_table, c->mask, c->d_claim, c->d_dirstate, d_keys, d_acts, d_silos, n, c->cfg.n_act, c->n_silos,
                              d_act_keys, n_act_keys, c->d_dslot, d_status, d_dropped_act, d_dropped_silo,
-                             reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st);
+                             reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st, dir_tags(c, d_tags, d_draws, nullptr));
     if (e) return hipfail(c, (hipError_t)e, "directory merge launch");
     c->count_ub += n;
     c->mirror_stale = true;
     probe_after_device_mutation(c);
+    return ORL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orl_dir_insert_single_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                                 size_t n, uint32_t* d_wact, uint8_t* d_wsilo, uint8_t* d_status, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!d_keys || !d_acts || !d_silos || !d_status)) return fail(c, ORL_E_INVALID, "null device buffer");
+    return dir_insert_device(c, d_keys, d_acts, d_silos, nullptr, n, d_wact, d_wsilo, nullptr, d_status, stream);
+}
+
+int orl_dir_insert_single_versioned_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts,
+                                           const uint8_t* d_silos, const int32_t* d_tags, size_t n, uint32_t* d_wact,
+                                           uint8_t* d_wsilo, int32_t* d_wtag, uint8_t* d_status, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_versions(c, true)) return r;
+    if (n && (!d_keys || !d_acts || !d_silos || !d_tags || !d_status)) return fail(c, ORL_E_INVALID, "null device buffer");
+    return dir_insert_device(c, d_keys, d_acts, d_silos, d_tags, n, d_wact, d_wsilo, d_wtag, d_status, stream);
+}
+
+int orl_dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
+                         const orl_grain_key* d_act_keys, uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act,
+                         uint8_t* d_dropped_silo, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (n && (!d_keys || !d_acts || !d_silos || !d_status || !d_act_keys)) return fail(c, ORL_E_INVALID, "null device buffer");
+    return dir_merge_device(c, d_keys, d_acts, d_silos, nullptr, nullptr, n, d_act_keys, n_act_keys, d_status, d_dropped_act,
+                            d_dropped_silo, stream);
+}
+
+int orl_dir_merge_versioned_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                                   const int32_t* d_tags, const int32_t* d_draws, size_t n, const orl_grain_key* d_act_keys,
+                                   uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act, uint8_t* d_dropped_silo,
+                                   void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_versions(c, true)) return r;
+    if (n && (!d_keys || !d_acts || !d_silos || !d_tags || !d_draws || !d_status || !d_act_keys))
+        return fail(c, ORL_E_INVALID, "null device buffer");
+    return dir_merge_device(c, d_keys, d_acts, d_silos, d_tags, d_draws, n, d_act_keys, n_act_keys, d_status, d_dropped_act,
+                            d_dropped_silo, stream);
+}
+
+int orl_dir_lookup_many_device(orl_ctx* c, const orl_grain_key* d_keys, const int32_t* d_etags, size_t n, uint8_t* d_kind,
+                               int32_t* d_etag_out, uint32_t* d_act, uint8_t* d_silo, uint64_t* d_counts, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_versions(c, true)) return r;
+    if (n && (!d_keys || !d_etags || !d_kind || !d_etag_out || !d_act || !d_silo)) return fail(c, ORL_E_INVALID, "null device buffer");
+    int r = sync_device_state(c);  // ORL_E_STATE on a host-only context; host-side changes go up first
+    if (r) return r;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int e = launch_lookup_many(c->d_params, c->d_table, c->mask, c->d_vtag, d_keys, d_etags, n, d_kind, d_etag_out, d_act, d_silo,
+                               d_counts, st);
+    if (e) return hipfail(c, (hipError_t)e, "lookup-many launch");
     return ORL_OK;
 }
 
@@ -1977,12 +2152,19 @@ int orl_dir_compact(orl_ctx* c) {
     std::vector<DirSlot> old;
     old.swap(c->table);
     c->table.assign(old.size(), DirSlot{});
+    std::vector<int32_t> old_tags;
+    if (c->versions) {
+        old_tags.swap(c->vtag);
+        c->vtag.assign(old.size(), 0);
+    }
     c->count = c->tombs = 0;
-    for (const DirSlot& d : old) {  // re-insert every live entry in slot order (lookups are layout-independent)
+    for (size_t o = 0; o < old.size(); ++o) {  // re-insert every live entry in slot order (lookups are layout-independent)
+        const DirSlot& d = old[o];
         if (d.state != SLOT_FULL) continue;
         uint64_t i = dir_slot(jenkins3(d.tcd, d.n0, d.n1), c->mask);
         while (c->table[i].state != SLOT_EMPTY) i = (i + 1) & c->mask;
         c->table[i] = d;
+        if (c->versions) c->vtag[i] = old_tags[o];  // the tag moves with its entry
         ++c->count;
     }
     c->dir_dirty = true;

@@ -299,6 +299,18 @@ struct CacheFresh {
     uint32_t pad = 0;
 };
 
+// ---- version tags of the partition (GrainInfo.VersionTag; orl_dir_versions_enable) --------------------
+// What the registration and merge kernels get beside their arguments (by value): slot == nullptr is a partition without
+// version tags, and every use sits behind that branch.  in[i] = message i's tag (the caller's rand.Next() draw of a
+// registration, the incoming copy's VersionTag of a merge), draws[i] = a merge's draw; a null array reads as zeros (the
+// unversioned calls on a versioned partition).  winner (optional) = the grain's tag after a registration.
+struct DirTags {
+    int32_t* slot = nullptr;  // one per table slot
+    const int32_t* in = nullptr;
+    const int32_t* draws = nullptr;
+    int32_t* winner = nullptr;
+};
+
 // ---- kernel launchers (route_kernels.hip) ---------------------------------------------------------
 // All return hipError_t as int; they only enqueue on `stream`.
 // KeyExt (string-key) directory slot, 48 B (round 5): the UniqueKey's 24 B, its KeyExt uniform hash, the activation
@@ -421,7 +433,7 @@ int launch_fanout_expand(const uint64_t* d_csr_off, const uint32_t* d_csr_tgt, c
 int launch_dir_insert(const RouteParams* d_params, DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt,
                       const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act,
                       uint32_t n_silos, uint32_t* d_slot, uint32_t* d_wact, uint8_t* d_wsilo, uint8_t* d_status, uint32_t* d_err,
-                      void* stream);
+                      void* stream, const DirTags& vt = DirTags{});
 int launch_cache_update(DirSlot* d_cache, uint64_t mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                         const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act, uint32_t n_silos, uint32_t* d_slot,
                         uint8_t* d_flag, uint32_t* d_err, void* stream, const RouteParams* d_params,
@@ -431,7 +443,8 @@ int launch_cache_gen_advance(const DirSlot* d_cache, uint64_t mask, uint64_t n, 
 int launch_dir_merge(DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                      const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act, uint32_t n_silos,
                      const orl_grain_key* d_act_keys, uint32_t n_act_keys, uint32_t* d_slot, uint8_t* d_status,
-                     uint32_t* d_dropped_act, uint8_t* d_dropped_silo, uint32_t* d_err, void* stream);
+                     uint32_t* d_dropped_act, uint8_t* d_dropped_silo, uint32_t* d_err, void* stream,
+                     const DirTags& vt = DirTags{});
 int launch_dir_remove(DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                       size_t n, uint32_t* d_slot, uint8_t* d_removed, void* stream);
 int launch_dir_split(const RouteParams* d_params, DirSlot* d_dir, uint64_t slots, uint32_t me, bool remove, uint64_t* d_cnt,

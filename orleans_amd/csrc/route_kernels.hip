@@ -4678,7 +4678,8 @@ __global__ __launch_bounds__(256) void k_dir_ins_probe(const RouteParams* __rest
                                                        uint32_t* __restrict__ claim, const orl_grain_key* __restrict__ keys,
                                                        const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos,
                                                        uint32_t n, uint32_t n_act, uint32_t n_silos, uint32_t* __restrict__ slot_out,
-                                                       uint8_t* __restrict__ status, uint32_t* __restrict__ err) {
+                                                       uint8_t* __restrict__ status, uint32_t* __restrict__ err,
+                                                       const int32_t* __restrict__ tags) {
     __shared__ RouteParams P;
     stage_params(&P, gp);
     __syncthreads();
@@ -4687,7 +4688,8 @@ __global__ __launch_bounds__(256) void k_dir_ins_probe(const RouteParams* __rest
     const orl_grain_key k = keys[i];
     const uint32_t silo = silos[i], cat = (uint32_t)(k.type_code_data >> 56);
     uint8_t st;
-    if (acts[i] >= n_act || silo >= n_silos || cat == ORL_CAT_KEYEXT_GRAIN || cat == ORL_CAT_SYSTEM_TARGET) {
+    if (acts[i] >= n_act || silo >= n_silos || cat == ORL_CAT_KEYEXT_GRAIN || cat == ORL_CAT_SYSTEM_TARGET ||
+        (tags && tags[i] < 0)) {  // a versioned registration's draw is a Random.Next(): never negative
         st = ORL_INS_UNSUPPORTED;
     } else {
         const uint32_t owner = dir_owner(P, k, silo);
@@ -4717,33 +4719,39 @@ __global__ __launch_bounds__(256) void k_dir_ins_resolve(const DirSlot* __restri
                                                          const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos,
                                                          uint32_t n, const uint32_t* __restrict__ slot_in,
                                                          uint8_t* __restrict__ status, uint32_t* __restrict__ wact,
-                                                         uint8_t* __restrict__ wsilo) {
+                                                         uint8_t* __restrict__ wsilo, DirTags vt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint8_t st = status[i];
     const uint32_t slot = slot_in[i] & kSlotMask;
     uint32_t a = ORL_NO_ACT;
     uint8_t sl = (uint8_t)ORL_NULL_SILO;
+    int32_t wt = ORL_DIR_NO_ETAG;
     if (st == kInsCandidate) {
         const uint32_t c = claim[slot];
         a = acts[c];
         sl = silos[c];
+        if (vt.winner) wt = vt.in ? vt.in[c] : 0;  // the tag the slot's winner commits below
         status[i] = c == i ? (uint8_t)ORL_INS_INSERTED : (uint8_t)ORL_INS_EXISTING;
     } else if (st == ORL_INS_EXISTING) {
         a = dir[slot].act;
         sl = dir[slot].silo;
+        if (vt.winner) wt = vt.slot[slot];  // an entry from before the batch: no registration changes its tag
     }
     if (wact) wact[i] = a;
     if (wsilo) wsilo[i] = sl;
+    if (vt.winner) vt.winner[i] = wt;
 }
 
 __global__ __launch_bounds__(256) void k_dir_ins_commit(DirSlot* __restrict__ dir, uint32_t* __restrict__ claim,
                                                         const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos,
                                                         uint32_t n, const uint32_t* __restrict__ slot_in,
-                                                        const uint8_t* __restrict__ status, uint64_t* __restrict__ cnt) {
+                                                        const uint8_t* __restrict__ status, uint64_t* __restrict__ cnt,
+                                                        DirTags vt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || status[i] != ORL_INS_INSERTED) return;
     const uint32_t slot = slot_in[i] & kSlotMask;
+    if (vt.slot) vt.slot[slot] = vt.in ? vt.in[i] : 0;  // VersionTag = rand.Next() (GrainInfo.AddSingleActivation :111)
     uint64_t* w24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(dir + slot) + 24);
     *w24 = (uint64_t)acts[i] | ((uint64_t)silos[i] << 32) | ((uint64_t)SLOT_FULL << 40);
     claim[slot] = kSlotNone;
@@ -5027,14 +5035,15 @@ __global__ __launch_bounds__(256) void k_dir_merge_probe(DirSlot* __restrict__ d
                                                          const orl_grain_key* __restrict__ keys, const uint32_t* __restrict__ acts,
                                                          const uint8_t* __restrict__ silos, uint32_t n, uint32_t n_act,
                                                          uint32_t n_silos, uint32_t n_act_keys, uint32_t* __restrict__ slot_out,
-                                                         uint8_t* __restrict__ status, uint32_t* __restrict__ err) {
+                                                         uint8_t* __restrict__ status, uint32_t* __restrict__ err, DirTags vt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const orl_grain_key k = keys[i];
     const uint32_t cat = (uint32_t)(k.type_code_data >> 56);
     uint32_t out = kSlotNone;
     uint8_t st = kInsCandidate;
-    if (acts[i] >= n_act || acts[i] >= n_act_keys || silos[i] >= n_silos || cat == ORL_CAT_KEYEXT_GRAIN) {
+    if (acts[i] >= n_act || acts[i] >= n_act_keys || silos[i] >= n_silos || cat == ORL_CAT_KEYEXT_GRAIN ||
+        (vt.in && vt.in[i] < 0) || (vt.draws && vt.draws[i] < 0)) {
         st = ORL_MERGE_UNSUPPORTED;
     } else {
         uint64_t slot = 0;
@@ -5092,12 +5101,19 @@ __global__ __launch_bounds__(256) void k_dir_merge_resolve(const DirSlot* __rest
 __global__ __launch_bounds__(256) void k_dir_merge_commit(DirSlot* __restrict__ dir, uint32_t* __restrict__ claim,
                                                           const uint32_t* __restrict__ acts, const uint8_t* __restrict__ silos,
                                                           uint32_t n, const uint32_t* __restrict__ slot_in,
-                                                          const uint8_t* __restrict__ status, uint64_t* __restrict__ cnt) {
+                                                          const uint8_t* __restrict__ status, uint64_t* __restrict__ cnt,
+                                                          DirTags vt) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint8_t st = status[i];
     if (st == ORL_MERGE_UNSUPPORTED || st == ORL_MERGE_DUPLICATE) return;
     const uint32_t slot = slot_in[i] & kSlotMask;
+    if (vt.slot) {
+        // an absent grain's GrainInfo is added as is, tag included (GrainDirectoryPartition.Merge :366-383); GrainInfo.Merge
+        // added an instance to a present one, so it drew a new tag whichever activation survives (:146-160)
+        if (st == ORL_MERGE_INSERTED) vt.slot[slot] = vt.in ? vt.in[i] : 0;
+        else if (st == ORL_MERGE_KEPT || st == ORL_MERGE_REPLACED) vt.slot[slot] = vt.draws ? vt.draws[i] : 0;
+    }
     if (st == ORL_MERGE_INSERTED || st == ORL_MERGE_REPLACED) {
         uint64_t* w24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(dir + slot) + 24);
         *w24 = (uint64_t)acts[i] | ((uint64_t)silos[i] << 32) | ((uint64_t)SLOT_FULL << 40);
@@ -6343,30 +6359,30 @@ int launch_partition_by_owner(const RouteParams* d_params, const orl_msg_hdr* d_
 int launch_dir_insert(const RouteParams* d_params, DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt,
                       const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act,
                       uint32_t n_silos, uint32_t* d_slot, uint32_t* d_wact, uint8_t* d_wsilo, uint8_t* d_status, uint32_t* d_err,
-                      void* stream) {
+                      void* stream, const DirTags& vt) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return 0;
     const dim3 g(ceil_div(n, 256)), b(256);
     hipLaunchKernelGGL(k_dir_ins_probe, g, b, 0, st, d_params, d_dir, dir_mask, d_claim, d_keys, d_acts, d_silos, (uint32_t)n,
-                       n_act, n_silos, d_slot, d_status, d_err);
+                       n_act, n_silos, d_slot, d_status, d_err, vt.slot ? vt.in : nullptr);
     hipLaunchKernelGGL(k_dir_ins_resolve, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_status, d_wact,
-                       d_wsilo);
-    hipLaunchKernelGGL(k_dir_ins_commit, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_status, d_cnt);
+                       d_wsilo, vt);
+    hipLaunchKernelGGL(k_dir_ins_commit, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_status, d_cnt, vt);
     return (int)hipGetLastError();
 }
 
 int launch_dir_merge(DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt, const orl_grain_key* d_keys,
                      const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act, uint32_t n_silos,
                      const orl_grain_key* d_act_keys, uint32_t n_act_keys, uint32_t* d_slot, uint8_t* d_status,
-                     uint32_t* d_dropped_act, uint8_t* d_dropped_silo, uint32_t* d_err, void* stream) {
+                     uint32_t* d_dropped_act, uint8_t* d_dropped_silo, uint32_t* d_err, void* stream, const DirTags& vt) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return 0;
     const dim3 g(ceil_div(n, 256)), b(256);
     hipLaunchKernelGGL(k_dir_merge_probe, g, b, 0, st, d_dir, dir_mask, d_claim, d_keys, d_acts, d_silos, (uint32_t)n, n_act,
-                       n_silos, n_act_keys, d_slot, d_status, d_err);
+                       n_silos, n_act_keys, d_slot, d_status, d_err, vt);
     hipLaunchKernelGGL(k_dir_merge_resolve, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, d_act_keys, (uint32_t)n, d_slot,
                        d_status, d_dropped_act, d_dropped_silo);
-    hipLaunchKernelGGL(k_dir_merge_commit, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_status, d_cnt);
+    hipLaunchKernelGGL(k_dir_merge_commit, g, b, 0, st, d_dir, d_claim, d_acts, d_silos, (uint32_t)n, d_slot, d_status, d_cnt, vt);
     return (int)hipGetLastError();
 }
 

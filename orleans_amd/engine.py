@@ -15,6 +15,9 @@ unregister                     LocalGrainDirectory.UnregisterAsync (:587-612) â†
 address_messages               Dispatcher.AddressMessage (src/OrleansRuntime/Core/Dispatcher.cs:555-579) for a
                                batch, + per-activation FIFO grouping (ActivationData.cs:483-514)
 hash_batch                     GrainId.GetUniformHashCode (src/Orleans/IDs/GrainId.cs:211-214)
+register_single_activation_    AddSingleActivation with the caller's rand.Next() draw as GrainInfo.VersionTag
+versioned                      (GrainDirectoryPartition.cs:100-114, 270-287)
+lookup_many(_device)           RemoteGrainDirectory.LookUpMany (RemoteGrainDirectory.cs:349-380)
 =============================  ==================================================================
 
 Error behaviour: API errors raise ``OrleansRouteError`` (the reference throws ArgumentException /
@@ -504,6 +507,60 @@ class GrainDirectoryEngine:
         by another silo â†’ (d_keys, d_acts, d_silos)[: *d_n_out], tombstoned here with `remove`."""
         self._ck(self._lib.orl_dir_split_device(self._ctx, int(me), L.SPLIT_REMOVE if remove else 0, ptr(d_keys),
                                                 ptr(d_acts), ptr(d_silos), int(cap), ptr(d_n_out), ptr(stream)))
+
+    # ---- version tags and LookUpMany (the owner's side of the cache refresh) ----
+    def enable_directory_versions(self) -> None:
+        """One GrainInfo.VersionTag per partition entry (orl_dir_versions_enable); entries already present get 0."""
+        self._ck(self._lib.orl_dir_versions_enable(self._ctx))
+
+    def register_single_activation_versioned(self, keys: np.ndarray, acts: np.ndarray, silos: np.ndarray, tags: np.ndarray):
+        """register_single_activation with tags[i] = message i's rand.Next() draw (>= 0), stored when message i inserts
+        (GrainDirectoryPartition.AddSingleActivation returns the tag, :270-287).  Returns (status, winner act, winner
+        silo, winner tag); the tag is DIR_NO_ETAG unless the status is INSERTED or EXISTING."""
+        keys = np.ascontiguousarray(keys, dtype=L.KEY_DTYPE)
+        acts = np.ascontiguousarray(acts, dtype=np.uint32)
+        silos = np.ascontiguousarray(silos, dtype=np.uint8)
+        tags = np.ascontiguousarray(tags, dtype=np.int32)
+        n = len(keys)
+        assert len(acts) == n and len(silos) == n and len(tags) == n
+        st, wa, ws, wt = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        self._ck(self._lib.orl_dir_insert_single_versioned(self._ctx, ptr(keys), ptr(acts), ptr(silos), ptr(tags), n, ptr(wa),
+                                                           ptr(ws), ptr(wt), ptr(st)))
+        return st, wa, ws, wt
+
+    def register_single_activation_versioned_device(self, d_keys, d_acts, d_silos, d_tags, n: int, d_status,
+                                                    d_winner_act=None, d_winner_silo=None, d_winner_tag=None,
+                                                    stream=None) -> None:
+        """register_single_activation_device with the draws d_tags (int32); a negative one gives INS_UNSUPPORTED."""
+        self._ck(self._lib.orl_dir_insert_single_versioned_device(self._ctx, ptr(d_keys), ptr(d_acts), ptr(d_silos),
+                                                                  ptr(d_tags), int(n), ptr(d_winner_act), ptr(d_winner_silo),
+                                                                  ptr(d_winner_tag), ptr(d_status), ptr(stream)))
+
+    def merge_directory_versioned_device(self, d_keys, d_acts, d_silos, d_tags, d_draws, n: int, d_act_keys, n_act_keys: int,
+                                         d_status, d_dropped_act=None, d_dropped_silo=None, stream=None) -> None:
+        """merge_directory_device with the incoming copy's VersionTags (stored by MERGE_INSERTED) and one draw per entry
+        (stored by MERGE_KEPT / MERGE_REPLACED: GrainInfo.Merge modified the entry, GrainDirectoryPartition.cs:146-160)."""
+        self._ck(self._lib.orl_dir_merge_versioned_device(self._ctx, ptr(d_keys), ptr(d_acts), ptr(d_silos), ptr(d_tags),
+                                                          ptr(d_draws), int(n), ptr(d_act_keys), int(n_act_keys),
+                                                          ptr(d_status), ptr(d_dropped_act), ptr(d_dropped_silo), ptr(stream)))
+
+    def lookup_many_device(self, d_keys, d_etags, n: int, d_kind, d_etag_out, d_act, d_silo, d_counts=None,
+                           stream=None) -> None:
+        """RemoteGrainDirectory.LookUpMany (RemoteGrainDirectory.cs:349-380) over device arrays, on `stream`: per request
+        a LUM_* kind, the entry's current tag (or DIR_NO_ETAG) and, for LUM_UPDATED, the activation.  d_keys / d_etags may
+        be slices of another context's cache_maintain_device lists.  d_counts: 5 uint64 (written)."""
+        self._ck(self._lib.orl_dir_lookup_many_device(self._ctx, ptr(d_keys), ptr(d_etags), int(n), ptr(d_kind),
+                                                      ptr(d_etag_out), ptr(d_act), ptr(d_silo), ptr(d_counts), ptr(stream)))
+
+    def lookup_many(self, keys: np.ndarray, etags: np.ndarray):
+        """LookUpMany on the host mirror (orl_dir_lookup_many_host): (kind, etag, act, silo) arrays."""
+        keys = np.ascontiguousarray(keys, dtype=L.KEY_DTYPE)
+        etags = np.ascontiguousarray(etags, dtype=np.int32)
+        n = len(keys)
+        assert len(etags) == n
+        kind, eo, a, s = np.zeros(n, np.uint8), np.zeros(n, np.int32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._ck(self._lib.orl_dir_lookup_many_host(self._ctx, ptr(keys), ptr(etags), n, ptr(kind), ptr(eo), ptr(a), ptr(s)))
+        return kind, eo, a, s
 
     # ---- stream / reminder rings (SURVEY Â§8(f) f3) ----
     def vring_set_buckets(self, buckets_per_silo: int) -> None:
