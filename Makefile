@@ -18,7 +18,7 @@ build/route_kernels.o: orleans_amd/csrc/route_kernels.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/cache_evict.o: orleans_amd/csrc/cache_evict.hip orleans_amd/csrc/cache_evict.h $(HDR)
+build/cache_evict.o: orleans_amd/csrc/cache_evict.hip orleans_amd/csrc/cache_evict.h orleans_amd/csrc/cache_adaptive.h $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

@@ -493,7 +493,7 @@ struct orl_cache_stats {
     uint64_t entries;        /* live entries */
     uint64_t tombstones;     /* slots freed by an eviction or a removal and not reused yet */
     uint64_t evictions;      /* entries AdjustSize freed since orl_cache_config */
-    uint64_t evict_batches;  /* adds that took the device eviction path */
+    uint64_t evict_batches;  /* adds (and refresh applies) that took the device eviction path */
     uint64_t rebuilds;       /* tombstone compactions on the device */
     uint64_t host_fallbacks; /* adds handled by the host LRU (ORL_CACHE_EVICT_HOST only) */
 };
@@ -538,22 +538,47 @@ int orl_cache_evict_mode(orl_ctx* ctx, uint32_t mode);
  *   gives act ORL_NO_ACT, silo ORL_NULL_SILO, etag ORL_CACHE_NO_ETAG.  Every output is optional; the last four need an
  *   adaptive cache.
  *
- * ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) on the host: split the owner's response into
- * maximal runs of one kind and issue them in order — an activation list returned: orl_cache_add_or_update_versioned_device
- * with the returned etag; etag -1 and no list: orl_cache_remove_device; an etag only: orl_cache_mark_fresh_device.  That is
- * the reference's sequential loop.
+ * orl_cache_apply_refresh_device: ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) over the
+ *   owner's whole answer in one call, on the caller's stream.  The five input arrays are what
+ *   orl_dir_lookup_many_device reads and writes — the sweep's d_keys, the owner's d_kind, d_etag_out, d_act, d_silo — passed
+ *   on unchanged.  The result is, bit for bit, the reference's sequential loop over entries 0 .. n-1:
+ *     d_kind[i]                                  operation                                                       reference
+ *     ORL_LUM_UPDATED                            ADD: AddOrUpdate(key, (act, silo), etag); LRU.Add runs            :181-186
+ *                                                AdjustSize first; the new entry gets the etag, the initial
+ *                                                timer, LastRefreshed = now and is unaccessed
+ *     ORL_LUM_ABSENT, ORL_LUM_UNSUPPORTED,       REMOVE (the empty list for the reason given below)               :187-194
+ *     ORL_LUM_UPDATED_EMPTY
+ *     ORL_LUM_UNCHANGED                          FRESH: MarkAsFresh, exactly as orl_cache_mark_fresh_device        :195-204
+ *                                                leaves an entry (timer growth, LastRefreshed = now, most
+ *                                                recently used, the access mark as it was)
+ *     anything else                              ignored: no step
+ *   An ADD that fails the add's validity predicate (an unknown silo, ORL_NO_ACT, a handle >= n_act on a local silo) is
+ *   ignored like an unknown kind.  Entry i stamps G + i + 1 and G advances by n, ignored entries included.  A response names
+ *   a grain once: of the entries on one key that would take a step, the first applies and the later ones are ignored.
+ *   d_present[i] (optional) = 1 when the operation found its key in the cache at its turn (an ADD updated rather than
+ *   inserted — after its AdjustSize, which at capacity can free the very key it updates; a REMOVE removed; a FRESH found),
+ *   0 otherwise and for ignored entries.  d_counts (optional, device u64[4]) is written, not accumulated: {ADDs, REMOVEs,
+ *   FRESHes, ignored}, the first three the reference's cnt1..cnt3.  n > max_batch: ORL_E_CAPACITY; a null input array with
+ *   n > 0: ORL_E_INVALID; n = 0 writes d_counts and nothing else.  In orl_cache_stats, evict_batches counts a call whose
+ *   bounds on the host allowed an eviction, whether or not the response held an ADD (only the device knows).
  *
- * The whole refresh, device to device (DESIGN §13):
+ * ProcessCacheRefreshResponse is orl_cache_apply_refresh_device.  The documented alternative composes it on the host:
+ * split the owner's response into maximal runs of one kind and issue them in order — an activation list returned:
+ * orl_cache_add_or_update_versioned_device with the returned etag; etag -1 and no list: orl_cache_remove_device; an etag
+ * only: orl_cache_mark_fresh_device.  That is the reference's sequential loop too, at the cost of a copy of the kinds to the
+ * host and one call per run (about 0.62 n runs for a response that is half unchanged, a quarter updated, a quarter absent).
+ *
+ * The whole refresh, device to device (DESIGN §13, §14):
  *   1. requester: orl_cache_maintain_device → per owner o the lists d_keys + off[o], d_etags + off[o] (device pointers);
  *   2. owner o (a context with orl_dir_versions_enable): orl_dir_lookup_many_device on those pointers, unchanged when
  *      both contexts live in one process → per request a kind, the current tag and, for ORL_LUM_UPDATED, the activation;
- *   3. requester, per maximal run of one kind in request order: ORL_LUM_UPDATED → orl_cache_add_or_update_versioned_device
- *      with the returned activation and tag; ORL_LUM_ABSENT and ORL_LUM_UNSUPPORTED → orl_cache_remove_device;
- *      ORL_LUM_UNCHANGED → orl_cache_mark_fresh_device.
+ *   3. requester: orl_cache_apply_refresh_device on the request's keys and the owner's four output arrays, unchanged, in
+ *      pieces of at most max_batch entries (consecutive pieces by pointer offset: the loop is sequential, so cutting it is
+ *      exact).  No copy to the host in between.
  * ORL_LUM_UPDATED_EMPTY (the entry exists but its only activation sits on a silo that is not functional) is an empty
  * activation list with a tag in the reference, which the requester's AddOrUpdate would cache as such.  The device cache
- * holds one activation per grain and no empty lists, so the requester removes the entry (orl_cache_remove_device): the
- * next lookup misses either way, but the requester's entry count and LRU state differ from the reference's there. */
+ * holds one activation per grain and no empty lists, so the requester removes the entry: the next lookup misses either
+ * way, but the requester's entry count and LRU state differ from the reference's there. */
 #define ORL_CACHE_NO_ETAG (-1) /* GrainInfo.NO_ETAG */
 struct orl_cache_sweep {
     const orl_grain_key* d_keys;      /* the refresh lists, owner-major */
@@ -570,6 +595,9 @@ int orl_cache_maintain_device(orl_ctx* ctx, uint32_t me, uint32_t opts, int64_t 
                               void* stream);
 int orl_cache_mark_fresh_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, int64_t now_ticks, uint8_t* d_found,
                                 void* stream);
+int orl_cache_apply_refresh_device(orl_ctx* ctx, const orl_grain_key* d_keys, const uint8_t* d_kind, const int32_t* d_etags,
+                                   const uint32_t* d_acts, const uint8_t* d_silos, size_t n, int64_t now_ticks,
+                                   uint8_t* d_present, uint64_t* d_counts, void* stream);
 int orl_cache_adjust_for_removed_silo_device(orl_ctx* ctx, uint32_t me, uint32_t opts, uint32_t removed_silo,
                                              uint64_t* d_removed_count, void* stream);
 int orl_cache_peek_device(orl_ctx* ctx, const orl_grain_key* d_keys, size_t n, uint32_t* d_act, uint8_t* d_silo,

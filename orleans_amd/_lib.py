@@ -231,6 +231,7 @@ _SIGS = {
     "orl_cache_add_or_update_versioned_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int64, _P]),
     "orl_cache_maintain_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int64, _P, _P]),
     "orl_cache_mark_fresh_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int64, _P, _P]),
+    "orl_cache_apply_refresh_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int64, _P, _P, _P]),
     "orl_cache_adjust_for_removed_silo_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),
     "orl_cache_peek_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "orl_sw_types_set": (C.c_int, [_P, _P, _P, C.c_uint32]),

@@ -44,6 +44,23 @@ int launch_cache_adjust(const RouteParams* d_params, DirSlot* d_cache, uint64_t 
 int launch_cache_mark_fresh(DirSlot* d_cache, uint64_t mask, const orl_grain_key* d_keys, size_t n, int64_t now, int64_t max_ttl,
                             double growth, uint8_t* d_found, void* stream);
 
+#ifdef __HIPCC__
+// MarkAsFresh's change to a found entry (slot s of an adaptive table), shared by k_mark_fresh and the refresh apply
+// (cache_evict.hip k_ra_apply): TryGetValue takes the generation `stamp` — NumAccesses untouched, so `seen` follows the
+// stamp of an unaccessed entry — ExpirationTimer = Min(max, ExpirationTimer.Multiply(growth)) =
+// (long)((double)ticks * growth) (StandardExtensions.cs:34-39), LastRefreshed = now.
+__device__ __forceinline__ void cache_mark_fresh_slot(const DirSlot* cache, uint64_t mask, uint64_t s, unsigned long long stamp,
+                                                      int64_t now, int64_t max_ttl, double growth) {
+    const CacheAdaptive a = cache_adaptive(cache, mask);
+    unsigned long long* gen = reinterpret_cast<unsigned long long*>(const_cast<DirSlot*>(cache + mask + 1));
+    if (gen[s] == a.seen[s]) a.seen[s] = stamp;
+    gen[s] = stamp;
+    const int64_t grown = (int64_t)__dmul_rn(__ll2double_rn((long long)a.ttl[s]), growth);
+    a.ttl[s] = max_ttl < grown ? max_ttl : grown;
+    a.last_refreshed[s] = now;
+}
+#endif
+
 // A lookup that stamps nothing.  Every output optional; the last four need an adaptive table (adaptive = true).
 int launch_cache_peek(const DirSlot* d_cache, uint64_t mask, bool adaptive, const orl_grain_key* d_keys, size_t n, uint32_t* d_act,
                       uint8_t* d_silo, int32_t* d_etag, int64_t* d_ttl, int64_t* d_last_refreshed, uint8_t* d_accessed,

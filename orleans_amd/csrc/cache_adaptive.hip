@@ -288,14 +288,7 @@ __global__ __launch_bounds__(256) void k_mark_fresh(DirSlot* __restrict__ cache,
     const uint64_t s = find_slot(cache, mask, keys[i]);
     if (found) found[i] = s != ~0ull ? 1u : 0u;
     if (s == ~0ull) return;
-    const CacheAdaptive a = cache_adaptive(cache, mask);
-    unsigned long long* gen = gens_of(cache, mask);
-    const unsigned long long stamp = gen[mask + 1] + i + 1ull;
-    if (gen[s] == a.seen[s]) a.seen[s] = stamp;
-    gen[s] = stamp;
-    const int64_t grown = (int64_t)__dmul_rn(__ll2double_rn((long long)a.ttl[s]), growth);
-    a.ttl[s] = max_ttl < grown ? max_ttl : grown;
-    a.last_refreshed[s] = now;
+    cache_mark_fresh_slot(cache, mask, s, gens_of(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
 }
 
 __global__ __launch_bounds__(256) void k_peek(const DirSlot* __restrict__ cache, uint64_t mask, uint32_t adaptive,

@@ -23,6 +23,11 @@ struct CacheEvictScratch {
     uint8_t* ev_b = nullptr;        // the serial pass evicted this batch entry
     uint8_t* keep = nullptr;        // last occurrence of its key and not evicted: inserted / updated
     uint32_t* group_tab = nullptr;  // [group_mask + 1] claim table: one entry index per distinct key
+    // per entry of a refresh response [max_batch] (launch_cache_apply_refresh)
+    uint32_t* grp_b = nullptr;      // the key's claim-table slot
+    uint32_t* live_b = nullptr;     // the serial pass left this batch element in the queue (an ADD, a FRESH that found its key)
+    uint8_t* op_b = nullptr;        // the entry's operation: ignore / ADD / REMOVE / FRESH
+    uint8_t* present_b = nullptr;   // the serial pass found the entry's key in the cache at its turn
     // per candidate [min(2 * max_batch, slots)]
     uint64_t* cand_stamp = nullptr;
     uint64_t* cand_stamp_s = nullptr;  // sorted ascending (stable: ties by slot index)
@@ -53,6 +58,23 @@ int launch_cache_evict_add(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_i
                            const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
                            uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s, void* stream,
                            const CacheFresh& fresh = CacheFresh{});
+
+// ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) over a whole response, stream-ordered: per
+// entry AddOrUpdate, Remove or MarkAsFresh by d_kind[i] (an ORL_LUM_* value), exactly the sequential loop.
+// may_evict: the host's bounds allow an eviction, so the candidate selection and the serial pass are enqueued (each
+// leaves at once when the response holds no valid ADD); otherwise the data-parallel apply alone.  fresh: as for the add,
+// on an adaptive table (fresh.on != 0 is required).  d_present [n] and d_counts [4] optional.
+struct CacheRefresh {
+    const uint8_t* kind = nullptr;
+    int64_t max_ttl = 0;   // MarkAsFresh: ExpirationTimer = min(max_ttl, (int64)((double)timer * growth))
+    double growth = 0;
+    uint8_t* present = nullptr;
+    uint64_t* counts = nullptr;
+};
+int launch_cache_apply_refresh(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_into, uint64_t* d_cnt, uint64_t capacity,
+                               const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
+                               uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s,
+                               void* stream, const CacheFresh& fresh, const CacheRefresh& refresh, bool may_evict);
 
 // Tombstone compaction alone: the FULL slots of d_src, with their stamps and the generation base, rehashed into d_dst
 // (same geometry, no tombstones); the counters reset to {entries, 0}.  adaptive: both tables carry the per-slot adaptive

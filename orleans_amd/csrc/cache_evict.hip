@@ -12,6 +12,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "cache_adaptive.h"
 #include "cache_evict.h"
 
 namespace orl {
@@ -552,6 +553,300 @@ __global__ void k_rb_finish(const DirSlot* __restrict__ src, DirSlot* __restrict
     cnt[1] = 0;
 }
 
+// ---- a refresh response: one operation per entry (orl_cache_apply_refresh_device) ----------------------------------
+// ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) is the batch add's sequential process with
+// three kinds of step: AddOrUpdate (AdjustSize first), Remove, MarkAsFresh.  Same three phases; the keys of the entries
+// that take a step are distinct (a later occurrence of a key is ignored), so a batch element is never superseded and the
+// queue's batch part carries one bit, `live`: an ADD's element always, a FRESH's when it found its key, a REMOVE's never.
+// The counts that size the work (valid ADDs, operations) exist only on the device: every kernel of the selection and the
+// serial pass leaves at once when the response holds no ADD.
+
+enum : uint8_t { OP_IGNORE = 0, OP_ADD = 1, OP_REMOVE = 2, OP_FRESH = 3 };
+enum { ST_ADDS = 8, ST_REMOVES = 9, ST_FRESHES = 10 };  // after ST_REBUILT: the operations of the call
+
+// Per entry: its operation, the key's FULL slot (a read-only walk) and its claim-table group.  The claim keeps the
+// smallest index of a key's occurrences: a slot only ever goes from one occurrence of a key to an earlier one of the same.
+__global__ __launch_bounds__(256) void k_ra_prep(const DirSlot* __restrict__ cache, uint64_t mask, const orl_grain_key* __restrict__ keys,
+                                                 const uint8_t* __restrict__ kind, const uint32_t* __restrict__ acts,
+                                                 const uint8_t* __restrict__ silos, uint32_t n, uint32_t n_act, uint32_t n_silos,
+                                                 const uint32_t* __restrict__ local, uint32_t* group_tab, uint32_t gmask,
+                                                 uint32_t* __restrict__ old_slot, uint32_t* __restrict__ grp_b,
+                                                 uint8_t* __restrict__ op_b, uint64_t* __restrict__ cnt) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint8_t op = OP_IGNORE;
+    const uint32_t kd = kind[i];
+    if (kd == ORL_LUM_UPDATED) {
+        const uint32_t sl = silos[i], a = acts[i];  // k_cache_probe's predicate
+        if (sl < n_silos && (a < n_act || (a != ORL_NO_ACT && !mask_bit(local, sl)))) op = OP_ADD;
+    } else if (kd == ORL_LUM_ABSENT || kd == ORL_LUM_UNSUPPORTED || kd == ORL_LUM_UPDATED_EMPTY) {
+        op = OP_REMOVE;
+    } else if (kd == ORL_LUM_UNCHANGED) {
+        op = OP_FRESH;
+    }
+    uint32_t os = kNone, grp = kNone;
+    if (op != OP_IGNORE) {
+        const orl_grain_key k = keys[i];
+        const uint32_t h = jenkins3(k.type_code_data, k.n0, k.n1);
+        uint64_t cur = dir_slot(h, mask);
+        for (uint64_t step = 0; step <= mask; ++step) {
+            const uint32_t state = load_state(cache, cur);
+            if (state == SLOT_EMPTY) break;
+            if (state == SLOT_FULL && key_eq(cache, cur, k)) {
+                os = (uint32_t)cur;
+                break;
+            }
+            cur = (cur + 1) & mask;
+        }
+        uint32_t g = fmix32(h) & gmask;
+        for (uint32_t step = 0; step <= gmask; ++step) {
+            const uint32_t occ = atomicCAS(&group_tab[g], kNone, i);
+            if (occ == kNone) {
+                grp = g;
+                break;
+            }
+            const orl_grain_key o = keys[occ];
+            if (o.type_code_data == k.type_code_data && o.n0 == k.n0 && o.n1 == k.n1) {
+                atomicMin(&group_tab[g], i);
+                grp = g;
+                break;
+            }
+            g = (g + 1) & gmask;
+        }
+        if (grp == kNone) {  // group_tab holds >= 2 n entries: cannot be full
+            raise(cnt, kErrInvariant);
+            op = OP_IGNORE;
+        }
+    }
+    old_slot[i] = os;
+    grp_b[i] = grp;
+    op_b[i] = op;
+}
+
+// A key's first occurrence keeps its operation, the later ones are ignored; the operations are counted.
+__global__ __launch_bounds__(256) void k_ra_resolve(uint32_t n, const uint32_t* __restrict__ group_tab, const uint32_t* __restrict__ grp_b,
+                                                    uint8_t* __restrict__ op_b, uint8_t* __restrict__ ev_b, uint32_t* __restrict__ live_b,
+                                                    uint8_t* __restrict__ present_b, uint64_t* __restrict__ st) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint8_t op = OP_IGNORE;
+    if (i < n) {
+        op = op_b[i];
+        if (op != OP_IGNORE && group_tab[grp_b[i]] != i) op_b[i] = op = OP_IGNORE;
+        ev_b[i] = 0;
+        live_b[i] = 0;
+        present_b[i] = 0;
+    }
+    const int na = __syncthreads_count(op == OP_ADD), nr = __syncthreads_count(op == OP_REMOVE),
+              nf = __syncthreads_count(op == OP_FRESH);
+    if (threadIdx.x == 0) {
+        if (na) add64(&st[ST_ADDS], (uint64_t)na);
+        if (nr) add64(&st[ST_REMOVES], (uint64_t)nr);
+        if (nf) add64(&st[ST_FRESHES], (uint64_t)nf);
+    }
+}
+
+// k_ev_snapshot with K = min(entries, n_add + n_ops): at most n_add evictions, at most n_ops old entries skipped because
+// an earlier operation re-stamped or removed them.  No ADD: K = 0 and the table is not read.
+__global__ __launch_bounds__(256) void k_ra_snapshot(const DirSlot* __restrict__ cache, uint64_t mask, uint64_t* __restrict__ skey,
+                                                     uint64_t* __restrict__ st, uint32_t* __restrict__ hist,
+                                                     const uint64_t* __restrict__ cnt) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t n_add = st[ST_ADDS];
+    if (blockIdx.x == 0) {
+        hist[threadIdx.x] = 0;
+        if (threadIdx.x == 0) {
+            const uint64_t entries = cnt[0], bound = n_add + n_add + st[ST_REMOVES] + st[ST_FRESHES];
+            const uint64_t K = n_add == 0 ? 0 : (entries < bound ? entries : bound);
+            st[ST_K] = K;
+            st[ST_PREFIX] = 0;
+            st[ST_RANK] = K;
+        }
+    }
+    if (n_add == 0 || s > mask) return;
+    skey[s] = load_state(cache, s) == SLOT_FULL ? gens_of(cache, mask)[s] : ~0ull;
+}
+
+// prevpos of every entry that takes a step, and nxt of the candidates the response names (each by one entry).
+__global__ __launch_bounds__(256) void k_ra_prev(uint32_t n, const uint8_t* __restrict__ op_b, const uint32_t* __restrict__ old_slot,
+                                                 const uint32_t* __restrict__ slotpos, const uint64_t* __restrict__ st,
+                                                 uint32_t* __restrict__ prevpos, uint32_t* __restrict__ nxt_c) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (st[ST_ADDS] == 0 || i >= n) return;
+    uint32_t pp = kNone;
+    if (op_b[i] == OP_IGNORE) {
+        pp = kInvalid;
+    } else if (old_slot[i] != kNone) {
+        const uint32_t cp = slotpos[old_slot[i]];
+        if (cp != kNone) {
+            pp = cp;
+            nxt_c[cp] = i;
+        } else {
+            pp = kAlways;
+        }
+    }
+    prevpos[i] = pp;
+}
+
+// k_ev_serial with an operation per entry.  The queue's batch part is read from live_b (written by the stepping lane in
+// earlier rounds, and patched into the staged window when the element lies inside it).
+__global__ __launch_bounds__(256) void k_ra_serial(const uint32_t* __restrict__ nxt_c, const uint8_t* __restrict__ op_b,
+                                                   const uint32_t* __restrict__ prevpos, uint32_t n, uint64_t capacity,
+                                                   uint64_t* __restrict__ cnt, uint64_t* __restrict__ st, uint8_t* __restrict__ ev_c,
+                                                   uint8_t* __restrict__ ev_b, uint32_t* live_b, uint8_t* __restrict__ present_b) {
+    __shared__ uint32_t qbuf[kChunk], bbuf[kChunk];
+    __shared__ uint8_t obuf[kChunk];
+    __shared__ uint32_t s_p, s_i, s_done;
+    __shared__ uint64_t s_c, s_ev;
+    if (st[ST_ADDS] == 0) return;  // nothing can be evicted: every operation finds what the table held before the call
+    const uint32_t ncand = (uint32_t)st[ST_NCAND];
+    const uint64_t entries0 = cnt[0];
+    const uint64_t Q = (uint64_t)ncand + n;
+    if (threadIdx.x == 0) {
+        s_p = 0;
+        s_i = 0;
+        s_done = 0;
+        s_c = entries0;
+        s_ev = 0;
+    }
+    __syncthreads();
+    const uint64_t max_rounds = (Q + n) / kChunk + 4;
+    for (uint64_t round = 0; round < max_rounds; ++round) {
+        const uint32_t q0 = s_p, b0 = s_i;
+        if (s_done || b0 >= n) break;
+        for (uint32_t t = threadIdx.x; t < kChunk; t += 256u) {
+            const uint64_t q = (uint64_t)q0 + t;
+            uint32_t v = kInvalid;
+            if (q < ncand)
+                v = nxt_c[q];
+            else if (q < Q && __hip_atomic_load(&live_b[q - ncand], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                v = kNone;
+            qbuf[t] = v;
+            const uint64_t b = (uint64_t)b0 + t;
+            bbuf[t] = b < n ? prevpos[b] : kInvalid;
+            obuf[t] = b < n ? op_b[b] : (uint8_t)OP_IGNORE;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t p = q0, i = b0;
+            uint64_t c = s_c, ev = s_ev;
+            bool stop = false, bad = false;
+            while (i < n && i - b0 < kChunk && !stop) {
+                const uint32_t pp = bbuf[i - b0];
+                const uint32_t op = obuf[i - b0];
+                if (op == OP_IGNORE) {
+                    ++i;
+                    continue;
+                }
+                while (op == OP_ADD && c >= capacity && !stop) {  // AdjustSize
+                    // advance over batch elements that are not live and over candidates an operation before i took
+                    while (p - q0 < kChunk && p < Q && (qbuf[p - q0] == kInvalid || qbuf[p - q0] < i)) ++p;
+                    if (p >= Q || (p >= ncand && p - ncand >= i) || (p >= ncand && ncand < entries0)) {
+                        bad = stop = true;  // nothing left to evict / the pointer left the candidates
+                    } else if (p - q0 >= kChunk) {
+                        stop = true;  // refill the queue window, then resume at this entry
+                    } else {
+                        if (p < ncand) ev_c[p] = 1; else ev_b[p - ncand] = 1;
+                        ++p;
+                        --c;
+                        ++ev;
+                    }
+                }
+                if (stop) break;
+                const bool present = pp != kNone && (pp == kAlways || pp >= p);
+                bool live = false;
+                if (op == OP_ADD) {
+                    live = true;
+                    if (!present) ++c;
+                } else if (op == OP_REMOVE) {
+                    if (present) --c;
+                } else {
+                    live = present;
+                }
+                present_b[i] = present ? 1 : 0;
+                if (live) {
+                    __hip_atomic_store(&live_b[i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint64_t qp = (uint64_t)ncand + i;
+                    if (qp >= q0 && qp - q0 < kChunk) qbuf[qp - q0] = kNone;
+                }
+                ++i;
+            }
+            s_p = p;
+            s_i = i;
+            s_c = c;
+            s_ev = ev;
+            if (bad) {
+                raise(cnt, kErrInvariant);
+                s_done = 1;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (!s_done && s_i < n) raise(cnt, kErrInvariant);  // the round bound ran out
+        st[ST_FINAL] = s_c;
+        st[ST_EVICTED] = s_ev;
+        cnt[3] += s_ev;
+    }
+}
+
+// The apply of everything but the inserts: tombstones (a REMOVE's entry, the old slot of an evicted ADD or FRESH), the
+// state change of MarkAsFresh, `keep` for k_ev_insert, d_present.  serial == 0 (the host knows that nothing can be
+// evicted) or no ADD in the response: the serial pass did not run, and an operation is present when its key had a slot.
+__global__ __launch_bounds__(256) void k_ra_apply(DirSlot* __restrict__ cache, uint64_t mask, uint32_t n, const uint8_t* __restrict__ op_b,
+                                                  const uint8_t* __restrict__ ev_b, const uint8_t* __restrict__ present_b,
+                                                  const uint32_t* __restrict__ old_slot, const uint32_t* __restrict__ grp_b,
+                                                  uint32_t* __restrict__ group_tab, uint8_t* __restrict__ keep,
+                                                  uint8_t* __restrict__ d_present, uint64_t* __restrict__ cnt,
+                                                  const uint64_t* __restrict__ st, uint32_t serial, int64_t now, int64_t max_ttl,
+                                                  double growth) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool gone = false;
+    if (i < n) {
+        const uint32_t op = op_b[i];
+        bool present = false, kept = false;
+        if (op != OP_IGNORE) {
+            group_tab[grp_b[i]] = kNone;  // the key's first occurrence leaves the claim table clean for the next call
+            const bool ran = serial && st[ST_ADDS] != 0;
+            const uint32_t os = old_slot[i];
+            present = ran ? present_b[i] != 0 : os != kNone;
+            const bool evicted = ran && ev_b[i];
+            const bool full = os != kNone && cache[os].state == SLOT_FULL;  // not an evicted candidate (k_ev_tomb_c ran)
+            if (op == OP_ADD) {
+                if (evicted) gone = full; else kept = true;
+            } else if (op == OP_REMOVE) {
+                gone = full;
+            } else if (present && full) {
+                if (evicted)
+                    gone = true;
+                else
+                    cache_mark_fresh_slot(cache, mask, os, gens_of(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
+            }
+            if (gone) cache[os].state = SLOT_TOMB;
+        }
+        keep[i] = kept ? 1 : 0;
+        if (d_present) d_present[i] = present ? 1 : 0;
+    }
+    const int k = __syncthreads_count(gone ? 1 : 0);
+    if (threadIdx.x == 0 && k) {
+        add64(&cnt[0], ~(uint64_t)k + 1);
+        add64(&cnt[1], (uint64_t)k);
+    }
+}
+
+__global__ void k_ra_finish(DirSlot* __restrict__ cache, uint64_t mask, uint64_t n, uint64_t* __restrict__ cnt,
+                            const uint64_t* __restrict__ st, uint32_t serial, uint64_t* __restrict__ d_counts) {
+    if (threadIdx.x != 0) return;
+    if (serial && st[ST_ADDS] != 0 && cnt[0] != st[ST_FINAL]) raise(cnt, kErrInvariant);  // as k_ev_finish
+    gens_of(cache, mask)[mask + 1] += n;
+    if (d_counts) {
+        const uint64_t a = st[ST_ADDS], r = st[ST_REMOVES], f = st[ST_FRESHES];
+        d_counts[0] = a;
+        d_counts[1] = r;
+        d_counts[2] = f;
+        d_counts[3] = n - a - r - f;
+    }
+}
+
 inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + 255) / 256); }
 
 size_t carve(size_t& off, size_t bytes) {
@@ -583,7 +878,8 @@ int cache_evict_alloc(CacheEvictScratch* s, uint64_t max_batch, uint64_t slots) 
                  o_gt = carve(off, groups * 4), o_cs = carve(off, ncap * 8), o_css = carve(off, ncap * 8),
                  o_cl = carve(off, ncap * 4), o_cls = carve(off, ncap * 4), o_nc = carve(off, ncap * 4), o_ec = carve(off, ncap),
                  o_sk = carve(off, slots * 8), o_sp = carve(off, slots * 4), o_tc = carve(off, (size_t)ntiles * 4),
-                 o_st = carve(off, 16 * 8), o_h = carve(off, 256 * 4), o_tmp = carve(off, temp);
+                 o_st = carve(off, 16 * 8), o_h = carve(off, 256 * 4), o_tmp = carve(off, temp), o_gb = carve(off, mb * 4),
+                 o_lb = carve(off, mb * 4), o_ob = carve(off, mb), o_prb = carve(off, mb);
     uint8_t* b = nullptr;
     if ((e = hipMalloc((void**)&b, off)) != hipSuccess) return (int)e;
     s->base = b;
@@ -598,6 +894,7 @@ int cache_evict_alloc(CacheEvictScratch* s, uint64_t max_batch, uint64_t slots) 
     s->cand_slot = (uint32_t*)(b + o_cl); s->cand_slot_s = (uint32_t*)(b + o_cls); s->nxt_c = (uint32_t*)(b + o_nc);
     s->ev_c = b + o_ec; s->skey = (uint64_t*)(b + o_sk); s->slotpos = (uint32_t*)(b + o_sp); s->tile_cnt = (uint32_t*)(b + o_tc);
     s->st = (uint64_t*)(b + o_st); s->hist = (uint32_t*)(b + o_h); s->sort_temp = b + o_tmp; s->sort_temp_bytes = temp;
+    s->grp_b = (uint32_t*)(b + o_gb); s->live_b = (uint32_t*)(b + o_lb); s->op_b = b + o_ob; s->present_b = b + o_prb;
     if ((e = hipMemset(b, 0, off)) != hipSuccess) return (int)e;
     if ((e = hipMemset(s->group_tab, 0xFF, groups * 4)) != hipSuccess) return (int)e;
     if ((e = hipMemset(s->slotpos, 0xFF, slots * 4)) != hipSuccess) return (int)e;
@@ -677,6 +974,63 @@ int launch_cache_evict_add(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_i
     }
     hipLaunchKernelGGL(k_ev_insert, gn, b, 0, st, into, mask, d_keys, d_acts, d_silos, un, s.keep, d_cnt, fresh);
     hipLaunchKernelGGL(k_ev_finish, dim3(1), dim3(64), 0, st, into, mask, (uint64_t)n, d_cnt, s.st);
+    return (int)hipGetLastError();
+}
+
+int launch_cache_apply_refresh(DirSlot* d_cache, uint64_t mask, DirSlot* d_rebuild_into, uint64_t* d_cnt, uint64_t capacity,
+                               const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n,
+                               uint32_t n_act, uint32_t n_silos, const uint32_t* d_local, const CacheEvictScratch& s,
+                               void* stream, const CacheFresh& fresh, const CacheRefresh& rf, bool may_evict) {
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t slots = mask + 1;
+    if (n == 0) return rf.counts ? (int)hipMemsetAsync(rf.counts, 0, 4 * 8, st) : 0;
+    if (n > s.max_batch || slots != s.slots || !fresh.on) return (int)hipErrorInvalidValue;
+    const uint32_t un = (uint32_t)n;
+    const uint32_t ncap = may_evict ? (uint32_t)std::min<uint64_t>(2 * (uint64_t)n, slots) : 0u;  // n_add + n_ops <= 2 n
+    const dim3 b(256), gn(blocks(n)), gc(blocks(std::max<uint32_t>(ncap, 1))), gs(blocks(slots)), gt(s.ntiles);
+    hipError_t e;
+    size_t tb = 0;
+    if (may_evict) {  // the sort's temporary storage was sized for max_batch by cache_evict_alloc
+        if ((e = rocprim::radix_sort_pairs(nullptr, tb, s.cand_stamp, s.cand_stamp_s, s.cand_slot, s.cand_slot_s, (size_t)ncap, 0u,
+                                           64u, st)) != hipSuccess)
+            return (int)e;
+        if (tb > s.sort_temp_bytes) return (int)hipErrorOutOfMemory;
+    }
+    hipLaunchKernelGGL(k_ev_fill, dim3(blocks(std::max<uint32_t>(ncap, 16))), b, 0, st, ncap, s.cand_stamp, s.cand_slot, s.nxt_c,
+                       s.ev_c, s.st);
+    hipLaunchKernelGGL(k_ra_prep, gn, b, 0, st, d_cache, mask, d_keys, rf.kind, d_acts, d_silos, un, n_act, n_silos, d_local,
+                       s.group_tab, s.group_mask, s.old_slot, s.grp_b, s.op_b, d_cnt);
+    hipLaunchKernelGGL(k_ra_resolve, gn, b, 0, st, un, s.group_tab, s.grp_b, s.op_b, s.ev_b, s.live_b, s.present_b, s.st);
+    if (may_evict) {
+        hipLaunchKernelGGL(k_ra_snapshot, gs, b, 0, st, d_cache, mask, s.skey, s.st, s.hist, d_cnt);
+        const dim3 gh(std::min<uint32_t>(blocks(slots), 2048));
+        for (int pass = 7; pass >= 0; --pass) {  // each leaves at once when K = 0
+            hipLaunchKernelGGL(k_ev_hist, gh, b, 0, st, s.skey, slots, (uint32_t)pass * 8u, s.st, s.hist);
+            hipLaunchKernelGGL(k_ev_pick, dim3(1), b, 0, st, s.st, s.hist, (uint32_t)pass * 8u, d_cnt);
+        }
+        hipLaunchKernelGGL(k_ev_ccount, gt, b, 0, st, s.skey, slots, s.st, s.tile_cnt);
+        hipLaunchKernelGGL(k_ev_cscan, dim3(1), b, 0, st, s.tile_cnt, s.ntiles, s.st, ncap, d_cnt);
+        hipLaunchKernelGGL(k_ev_cemit, gt, b, 0, st, s.skey, slots, s.st, s.tile_cnt, s.cand_stamp, s.cand_slot, ncap);
+        tb = s.sort_temp_bytes;
+        if ((e = rocprim::radix_sort_pairs(s.sort_temp, tb, s.cand_stamp, s.cand_stamp_s, s.cand_slot, s.cand_slot_s, (size_t)ncap,
+                                           0u, 64u, st)) != hipSuccess)
+            return (int)e;
+        hipLaunchKernelGGL(k_ev_mark, gc, b, 0, st, s.cand_slot_s, s.st, s.slotpos, slots);
+        hipLaunchKernelGGL(k_ra_prev, gn, b, 0, st, un, s.op_b, s.old_slot, s.slotpos, s.st, s.prevpos, s.nxt_c);
+        hipLaunchKernelGGL(k_ra_serial, dim3(1), b, 0, st, s.nxt_c, s.op_b, s.prevpos, un, capacity, d_cnt, s.st, s.ev_c, s.ev_b,
+                           s.live_b, s.present_b);
+        hipLaunchKernelGGL(k_ev_tomb_c, gc, b, 0, st, d_cache, slots, s.cand_slot_s, s.ev_c, s.st, s.slotpos, d_cnt);
+    }
+    const uint32_t serial = may_evict ? 1u : 0u;
+    hipLaunchKernelGGL(k_ra_apply, gn, b, 0, st, d_cache, mask, un, s.op_b, s.ev_b, s.present_b, s.old_slot, s.grp_b, s.group_tab,
+                       s.keep, rf.present, d_cnt, s.st, serial, fresh.now, rf.max_ttl, rf.growth);
+    DirSlot* into = d_cache;
+    if (d_rebuild_into) {
+        if (int r = launch_cache_rebuild(d_cache, d_rebuild_into, mask, d_cnt, s, stream, true)) return r;
+        into = d_rebuild_into;
+    }
+    hipLaunchKernelGGL(k_ev_insert, gn, b, 0, st, into, mask, d_keys, d_acts, d_silos, un, s.keep, d_cnt, fresh);
+    hipLaunchKernelGGL(k_ra_finish, dim3(1), dim3(64), 0, st, into, mask, (uint64_t)n, d_cnt, s.st, serial, rf.counts);
     return (int)hipGetLastError();
 }
 

@@ -2566,6 +2566,66 @@ int orl_cache_mark_fresh_device(orl_ctx* c, const orl_grain_key* d_keys, size_t 
     return ORL_OK;
 }
 
+// ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) over the owner's whole answer, on the
+// caller's stream (cache_evict.hip).  The path choice is the versioned add's, from the host's upper bounds
+// with n as the bound on new entries: no eviction possible → the data-parallel apply alone (after a compaction when the
+// load bound asks for one); else the selection and the serial pass are enqueued too — they leave at once on the device
+// when the response holds no valid ADD, which the host cannot know — with the compaction between the tombstoning and the
+// inserts when the load bound asks for it.  Removes only turn FULL slots into tombstones: the bounds hold as after a sweep.
+int orl_cache_apply_refresh_device(orl_ctx* c, const orl_grain_key* d_keys, const uint8_t* d_kind, const int32_t* d_etags,
+                                   const uint32_t* d_acts, const uint8_t* d_silos, size_t n, int64_t now_ticks,
+                                   uint8_t* d_present, uint64_t* d_counts, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (int r = need_adaptive(c)) return r;
+    if (n && (!d_keys || !d_kind || !d_etags || !d_acts || !d_silos)) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    c->cache_now = now_ticks;
+    int r = sync_device_state(c);
+    if (r) return r;
+    set_cache_on(c, true);
+    if ((r = sync_device_state(c))) return r;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const uint64_t mask = c->cache_slots - 1;
+    CacheFresh fresh;
+    fresh.etags = d_etags;
+    fresh.now = now_ticks;
+    fresh.initial_ttl = c->cache_initial_ttl;
+    fresh.on = 1;
+    CacheRefresh rf;
+    rf.kind = d_kind;
+    rf.max_ttl = c->cache_max_ttl;
+    rf.growth = c->cache_growth;
+    rf.present = d_present;
+    rf.counts = d_counts;
+    const bool evicts = c->cache_ub + n > c->cache_cap;
+    const uint64_t fresh_ub = evicts ? std::min<uint64_t>(n, c->cache_cap) : n;  // an evicting call leaves at most capacity entries
+    const bool crowded = (c->cache_ub + c->cache_tombs_ub + fresh_ub) * 8 > c->cache_slots * 7;
+    if (crowded && !evicts && n) {  // only tombstones in the way: compact first
+        int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st, true);
+        if (e) return hipfail(c, (hipError_t)e, "cache rebuild launch");
+        std::swap(c->d_cache, c->d_cache2);
+        ++c->cache_rebuilds;
+        c->cache_tombs_ub = 0;
+    }
+    int e = launch_cache_apply_refresh(c->d_cache, mask, crowded && evicts ? c->d_cache2 : nullptr, c->d_cstate, c->cache_cap, d_keys,
+                                       d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st, fresh, rf,
+                                       evicts);
+    if (e) return hipfail(c, (hipError_t)e, "cache refresh-apply launch");
+    if (n == 0) return ORL_OK;
+    const uint64_t occupied = c->cache_ub + c->cache_tombs_ub + fresh_ub;  // FULL + TOMB slots grow by at most the new entries
+    c->cache_ub = std::min(c->cache_ub + n, c->cache_cap);
+    c->cache_tombs_ub = occupied > c->cache_ub ? occupied - c->cache_ub : 0;
+    if (evicts) {
+        ++c->cache_evict_batches;
+        if (crowded) {
+            std::swap(c->d_cache, c->d_cache2);
+            ++c->cache_rebuilds;
+            c->cache_tombs_ub = 0;
+        }
+    }
+    return ORL_OK;
+}
+
 int orl_cache_adjust_for_removed_silo_device(orl_ctx* c, uint32_t me, uint32_t opts, uint32_t removed_silo,
                                              uint64_t* d_removed_count, void* stream) {
     if (!c) return ORL_E_INVALID;

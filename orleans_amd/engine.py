@@ -663,6 +663,37 @@ class GrainDirectoryEngine:
         """MarkAsFresh (AdaptiveGrainDirectoryCache.cs:150-159) per key; the keys of a batch must be distinct."""
         self._ck(self._lib.orl_cache_mark_fresh_device(self._ctx, ptr(d_keys), int(n), int(now_ticks), ptr(d_found), ptr(stream)))
 
+    def cache_apply_refresh_device(self, d_keys, d_kind, d_etags, d_acts, d_silos, n: int, now_ticks: int, d_present=None,
+                                   d_counts=None, stream=None) -> None:
+        """ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) over a whole response of at most
+        max_batch entries in one device call: per entry AddOrUpdate (LUM_UPDATED), Remove (LUM_ABSENT, LUM_UNSUPPORTED,
+        LUM_UPDATED_EMPTY) or MarkAsFresh (LUM_UNCHANGED), exactly the sequential loop.  The inputs are lookup_many_device's
+        arrays, unchanged.  d_present: n uint8, d_counts: 4 uint64 {ADDs, REMOVEs, FRESHes, ignored} (both optional)."""
+        self._ck(self._lib.orl_cache_apply_refresh_device(self._ctx, ptr(d_keys), ptr(d_kind), ptr(d_etags), ptr(d_acts),
+                                                          ptr(d_silos), int(n), int(now_ticks), ptr(d_present), ptr(d_counts),
+                                                          ptr(stream)))
+
+    def cache_apply_refresh(self, d_keys, d_kind, d_etags, d_acts, d_silos, n: int, now_ticks: int, d_present=None,
+                            d_counts=None, stream=None) -> int:
+        """cache_apply_refresh_device over a response of any length (a sweep lists up to `capacity` grains): consecutive
+        pieces of at most max_batch entries by pointer offset, in order — the loop is sequential, so cutting it is exact.
+        Arguments are raw device addresses (int), tensors or None.  d_counts (4 uint64 per piece) must then hold
+        4 * pieces values: piece j writes d_counts[4 j : 4 j + 4].  Returns the number of pieces."""
+        def at(a, byte_off):
+            p = ptr(a)
+            return None if p is None else (p.value or 0) + byte_off
+
+        mb, done, pieces = self.max_batch, 0, 0
+        while True:
+            m = min(mb, n - done)
+            self.cache_apply_refresh_device(at(d_keys, done * L.KEY_DTYPE.itemsize), at(d_kind, done), at(d_etags, done * 4),
+                                            at(d_acts, done * 4), at(d_silos, done), m, now_ticks, at(d_present, done),
+                                            at(d_counts, pieces * 32), stream)
+            done += m
+            pieces += 1
+            if done >= n:
+                return pieces
+
     def cache_adjust_for_removed_silo_device(self, me: int, removed_silo: int, d_removed_count=None,
                                              opts: int = L.OPT_EXCLUDE_IF_STOPPING, stream=None) -> None:
         """LocalGrainDirectory.AdjustLocalCache (:330-344); call it after remove_server.  Any cache, adaptive or plain."""
