@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cache_adaptive.h"
+#include "dir_table_dev.h"
 
 namespace orl {
 
@@ -22,47 +23,6 @@ constexpr uint32_t kOwners = 256;                   // silo indices are bytes
 
 // The sweep's verdict on a slot (the high byte of CacheSweepScratch::cls; the low byte is the owner).
 enum : uint32_t { CL_NONE = 0, CL_SELF = 1, CL_KEPT = 2, CL_EXPIRED = 3, CL_REFRESH = 4, CL_NULL = 5 };
-
-__device__ __forceinline__ bool mask_bit(const uint32_t* m, uint32_t i) { return (m[i >> 5] >> (i & 31u)) & 1u; }
-
-__device__ __forceinline__ unsigned long long* gens_of(const DirSlot* t, uint64_t mask) {
-    return reinterpret_cast<unsigned long long*>(const_cast<DirSlot*>(t + mask + 1));
-}
-__device__ __forceinline__ void add64(uint64_t* p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); }
-
-__device__ __forceinline__ void stage_params(RouteParams* sp, const RouteParams* __restrict__ gp) {
-    const uint4* src = reinterpret_cast<const uint4*>(gp);
-    uint4* dst = reinterpret_cast<uint4*>(sp);
-    for (uint32_t i = threadIdx.x; i < sizeof(RouteParams) / 16; i += blockDim.x) dst[i] = src[i];
-}
-
-// LocalGrainDirectory.CalculateTargetSilo (LocalGrainDirectory.cs:439-497) for caller `me`, as route_head's stages 1-2
-// compute it (route_kernels.hip): a system target is the caller's own, the membership-table grain is the seed's, an
-// empty ring is the caller's, else FindLast(hash <= h) over the ascending ring with the wrap-around, stepping over `me`
-// while it is excluded.  0xFF = null (and the membership grain without a seed, which the reference throws on).
-__device__ __forceinline__ uint32_t target_silo(const RouteParams& P, uint64_t tcd, uint64_t n0, uint64_t n1, uint32_t me,
-                                                bool excl_opt) {
-    if ((uint32_t)(tcd >> 56) == ORL_CAT_SYSTEM_TARGET) return me;
-    if (tcd == P.mem_tcd && n0 == P.mem_n0 && n1 == P.mem_n1) return P.seed;
-    const bool exclude_me = excl_opt && !mask_bit(P.running, me);
-    const int n = (int)P.ring_n;
-    if (n == 0) return exclude_me ? 0xFFu : me;
-    const int32_t h = (int32_t)jenkins3(tcd, n0, n1);
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (P.ring_hash[mid] <= h) lo = mid + 1; else hi = mid;
-    }
-    int idx = lo - 1;
-    if (idx >= 0 && exclude_me && P.ring_silo[idx] == me) --idx;
-    if (idx < 0) {
-        idx = n - 1;
-        if (exclude_me && P.ring_silo[idx] == me) {
-            if (n > 1) idx = n - 2; else return 0xFFu;
-        }
-    }
-    return P.ring_silo[idx];
-}
 
 // The table walk both the sweep and AdjustLocalCache use: tile `blockIdx.x`, round j, every wave reads 64 consecutive
 // slots (coalesced), and (wave, round, lane) ascending is slot order.
@@ -86,7 +46,7 @@ __global__ __launch_bounds__(256) void k_sw_classify(const RouteParams* __restri
     if (threadIdx.x < 8) ccnt[threadIdx.x] = 0;
     __syncthreads();
     const CacheAdaptive a = cache_adaptive(cache, mask);
-    const unsigned long long* gen = gens_of(cache, mask);
+    const unsigned long long* gen = cache_gens(cache, mask);
     uint32_t c[CL_NULL + 1] = {0, 0, 0, 0, 0, 0};
     for (uint32_t j = 0; j < kPerThread; ++j) {
         const uint64_t s = walk_slot(j);
@@ -94,7 +54,7 @@ __global__ __launch_bounds__(256) void k_sw_classify(const RouteParams* __restri
         const DirSlot d = cache[s];
         uint32_t verdict = CL_NONE, owner = 0xFFu;
         if (d.state == SLOT_FULL) {
-            owner = target_silo(P, d.tcd, d.n0, d.n1, me, excl != 0);
+            owner = target_silo<true>(P, d.tcd, d.n0, d.n1, me, excl != 0);
             if (owner >= n_silos) {
                 verdict = CL_NULL;  // "there's no other silo and we're shutting down, so skip this entry" (:86-89)
                 owner = 0xFFu;
@@ -201,7 +161,7 @@ __global__ __launch_bounds__(256) void k_sw_apply(DirSlot* __restrict__ cache, u
     }
     __syncthreads();
     const CacheAdaptive a = cache_adaptive(cache, mask);
-    unsigned long long* gen = gens_of(cache, mask);
+    unsigned long long* gen = cache_gens(cache, mask);
     const unsigned long long G = gen[mask + 1];
 #pragma unroll
     for (uint32_t j = 0; j < kPerThread; ++j) {
@@ -226,7 +186,7 @@ __global__ __launch_bounds__(256) void k_sw_apply(DirSlot* __restrict__ cache, u
 
 // G += the emitted count (the Gets' generations).
 __global__ void k_sw_finish(const DirSlot* __restrict__ cache, uint64_t mask, const uint64_t* __restrict__ counts) {
-    if (threadIdx.x == 0) gens_of(cache, mask)[mask + 1] += counts[CL_REFRESH - 1];
+    if (threadIdx.x == 0) cache_gens(cache, mask)[mask + 1] += counts[CL_REFRESH - 1];
 }
 
 // ---- AdjustLocalCache -----------------------------------------------------------------------------------------------
@@ -245,7 +205,7 @@ __global__ __launch_bounds__(256) void k_adjust(const RouteParams* __restrict__ 
         if (s > mask) continue;
         const DirSlot d = cache[s];
         if (d.state != SLOT_FULL) continue;
-        const uint32_t owner = target_silo(P, d.tcd, d.n0, d.n1, me, excl != 0);
+        const uint32_t owner = target_silo<true>(P, d.tcd, d.n0, d.n1, me, excl != 0);
         // 2) now owned by me (LocalGrainDirectory.cs:335-339); 1) the activation sat on the removed silo (:341-342:
         // RemoveActivations of a single-activation entry ends in Remove, :973-976)
         if ((owner < n_silos && mask_bit(P.local, owner)) || d.silo == removed_silo) {
@@ -264,19 +224,6 @@ __global__ __launch_bounds__(256) void k_adjust(const RouteParams* __restrict__ 
 
 // ---- per-key calls ---------------------------------------------------------------------------------------------------
 
-// The key's FULL slot (a read-only chain walk), or ~0.
-__device__ __forceinline__ uint64_t find_slot(const DirSlot* __restrict__ cache, uint64_t mask, const orl_grain_key& k) {
-    uint64_t cur = dir_slot(jenkins3(k.type_code_data, k.n0, k.n1), mask);
-    for (uint64_t step = 0; step <= mask; ++step) {
-        const DirSlot& d = cache[cur];
-        const uint8_t state = d.state;
-        if (state == SLOT_EMPTY) break;
-        if (state == SLOT_FULL && d.tcd == k.type_code_data && d.n0 == k.n0 && d.n1 == k.n1) return cur;
-        cur = (cur + 1) & mask;
-    }
-    return ~0ull;
-}
-
 // MarkAsFresh: TryGetValue (the next generation; NumAccesses untouched, so `seen` follows the stamp of an unaccessed
 // entry), ExpirationTimer = Min(max, ExpirationTimer.Multiply(growth)) — (long)((double)ticks * growth),
 // StandardExtensions.cs:34-39 — and LastRefreshed = now.
@@ -285,10 +232,10 @@ __global__ __launch_bounds__(256) void k_mark_fresh(DirSlot* __restrict__ cache,
                                                     uint8_t* __restrict__ found) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint64_t s = find_slot(cache, mask, keys[i]);
+    const uint64_t s = find_full<false>(cache, mask, keys[i]);
     if (found) found[i] = s != ~0ull ? 1u : 0u;
     if (s == ~0ull) return;
-    cache_mark_fresh_slot(cache, mask, s, gens_of(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
+    cache_mark_fresh_slot(cache, mask, s, cache_gens(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
 }
 
 __global__ __launch_bounds__(256) void k_peek(const DirSlot* __restrict__ cache, uint64_t mask, uint32_t adaptive,
@@ -297,7 +244,7 @@ __global__ __launch_bounds__(256) void k_peek(const DirSlot* __restrict__ cache,
                                               int64_t* __restrict__ last_refreshed, uint8_t* __restrict__ accessed) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint64_t s = find_slot(cache, mask, keys[i]);
+    const uint64_t s = find_full<false>(cache, mask, keys[i]);
     const bool hit = s != ~0ull;
     if (act) act[i] = hit ? cache[s].act : ORL_NO_ACT;
     if (silo) silo[i] = hit ? cache[s].silo : (uint8_t)ORL_NULL_SILO;
@@ -306,7 +253,7 @@ __global__ __launch_bounds__(256) void k_peek(const DirSlot* __restrict__ cache,
     if (etag) etag[i] = hit ? a.etag[s] : ORL_CACHE_NO_ETAG;
     if (ttl) ttl[i] = hit ? a.ttl[s] : 0;
     if (last_refreshed) last_refreshed[i] = hit ? a.last_refreshed[s] : 0;
-    if (accessed) accessed[i] = hit && gens_of(cache, mask)[s] > a.seen[s] ? 1u : 0u;
+    if (accessed) accessed[i] = hit && cache_gens(cache, mask)[s] > a.seen[s] ? 1u : 0u;
 }
 
 size_t carve(size_t& off, size_t bytes) {

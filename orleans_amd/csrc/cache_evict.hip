@@ -14,6 +14,7 @@
 
 #include "cache_adaptive.h"
 #include "cache_evict.h"
+#include "dir_table_dev.h"
 
 namespace orl {
 
@@ -29,25 +30,7 @@ constexpr uint32_t kErrInvariant = 2u;
 
 enum { ST_NVALID = 0, ST_K = 1, ST_PREFIX = 2, ST_RANK = 3, ST_NCAND = 4, ST_FINAL = 5, ST_EVICTED = 6, ST_REBUILT = 7 };
 
-__device__ __forceinline__ bool mask_bit(const uint32_t* m, uint32_t i) { return (m[i >> 5] >> (i & 31u)) & 1u; }
-
-__device__ __forceinline__ uint32_t* word28(const DirSlot* t, uint64_t slot) {
-    return reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(const_cast<DirSlot*>(t + slot)) + 28);  // {silo, state, pad}
-}
-__device__ __forceinline__ uint32_t load_state(const DirSlot* t, uint64_t slot) {
-    return (__hip_atomic_load(word28(t, slot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 8) & 0xFFu;
-}
-__device__ __forceinline__ bool key_eq(const DirSlot* t, uint64_t slot, const orl_grain_key& k) {
-    const uint64_t* w = reinterpret_cast<const uint64_t*>(t + slot);
-    return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k.type_code_data &&
-           __hip_atomic_load(w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k.n0 &&
-           __hip_atomic_load(w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k.n1;
-}
-__device__ __forceinline__ unsigned long long* gens_of(const DirSlot* t, uint64_t mask) {
-    return reinterpret_cast<unsigned long long*>(const_cast<DirSlot*>(t + mask + 1));
-}
 __device__ __forceinline__ void raise(uint64_t* cnt, uint32_t bit) { atomicOr(reinterpret_cast<uint32_t*>(cnt + 2), bit); }
-__device__ __forceinline__ void add64(uint64_t* p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v); }
 
 // Exclusive scan of one value per thread over a 256-thread block; *total gets the block's sum.
 __device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t* lds /* [256] */, uint32_t* total) {
@@ -95,18 +78,8 @@ __global__ __launch_bounds__(256) void k_ev_prep(const DirSlot* __restrict__ cac
         uint32_t os = kNone, grp = kNone;
         if (valid) {
             const orl_grain_key k = keys[i];
-            const uint32_t h = jenkins3(k.type_code_data, k.n0, k.n1);
-            uint64_t cur = dir_slot(h, mask);
-            for (uint64_t step = 0; step <= mask; ++step) {
-                const uint32_t state = load_state(cache, cur);
-                if (state == SLOT_EMPTY) break;
-                if (state == SLOT_FULL && key_eq(cache, cur, k)) {
-                    os = (uint32_t)cur;
-                    break;
-                }
-                cur = (cur + 1) & mask;
-            }
-            uint32_t g = fmix32(h) & gmask;
+            os = (uint32_t)find_full<true>(cache, mask, k);  // not found: ~0 truncates to kNone
+            uint32_t g = fmix32(jenkins3(k.type_code_data, k.n0, k.n1)) & gmask;
             for (uint32_t step = 0; step <= gmask; ++step) {
                 const uint32_t occ = atomicCAS(&group_tab[g], kNone, i);
                 if (occ == kNone) {
@@ -167,7 +140,7 @@ __global__ __launch_bounds__(256) void k_ev_snapshot(const DirSlot* __restrict__
         }
     }
     if (s > mask) return;
-    skey[s] = load_state(cache, s) == SLOT_FULL ? gens_of(cache, mask)[s] : ~0ull;
+    skey[s] = slot_state(cache, s) == SLOT_FULL ? cache_gens(cache, mask)[s] : ~0ull;
 }
 
 // One 8-bit digit of the radix select: counts, per digit value, the stamps that match the prefix found so far.
@@ -444,7 +417,7 @@ __global__ __launch_bounds__(256) void k_ev_insert(DirSlot* __restrict__ cache, 
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n || !keep[i]) return;
     const orl_grain_key k = keys[i];
-    unsigned long long* gen = gens_of(cache, mask);
+    unsigned long long* gen = cache_gens(cache, mask);
     const unsigned long long stamp = gen[mask + 1] + i + 1ull;
     // adaptive cache: the new GrainDirectoryCacheEntry's state goes where the stamp goes
     const auto fresh_state = [&](uint64_t slot) {
@@ -456,27 +429,21 @@ __global__ __launch_bounds__(256) void k_ev_insert(DirSlot* __restrict__ cache, 
         a.seen[slot] = stamp;
     };
     const uint64_t w24 = (uint64_t)acts[i] | ((uint64_t)silos[i] << 32) | ((uint64_t)SLOT_FULL << 40);
-    const uint64_t start = dir_slot(jenkins3(k.type_code_data, k.n0, k.n1), mask);
-    uint64_t cur = start;
-    for (uint64_t step = 0; step <= mask; ++step) {  // an equal FULL entry: update
-        const uint32_t state = load_state(cache, cur);
-        if (state == SLOT_EMPTY) break;
-        if (state == SLOT_FULL && key_eq(cache, cur, k)) {
-            uint64_t* p24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(cache + cur) + 24);
-            __hip_atomic_store(p24, w24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            gen[cur] = stamp;
-            fresh_state(cur);
-            return;
-        }
-        cur = (cur + 1) & mask;
+    const uint64_t old = find_full<true>(cache, mask, k);
+    if (old != ~0ull) {  // an equal FULL entry: update
+        uint64_t* p24 = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(cache + old) + 24);
+        __hip_atomic_store(p24, w24, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gen[old] = stamp;
+        fresh_state(old);
+        return;
     }
-    cur = start;
+    uint64_t cur = key_start(k, mask);
     for (uint64_t step = 0; step <= mask; ++step) {  // a new entry: the chain's first free slot nobody else takes
-        const uint32_t v = __hip_atomic_load(word28(cache, cur), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t v = __hip_atomic_load(slot_word28(cache, cur), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t state = (v >> 8) & 0xFFu;
         if (state == SLOT_EMPTY || state == SLOT_TOMB) {
             uint32_t expect = v;
-            if (__hip_atomic_compare_exchange_strong(word28(cache, cur), &expect, (uint32_t)SLOT_CLAIMING << 8, __ATOMIC_RELAXED,
+            if (__hip_atomic_compare_exchange_strong(slot_word28(cache, cur), &expect, (uint32_t)SLOT_CLAIMING << 8, __ATOMIC_RELAXED,
                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                 uint64_t* kw = reinterpret_cast<uint64_t*>(cache + cur);
                 __hip_atomic_store(kw, k.type_code_data, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -500,7 +467,7 @@ __global__ void k_ev_finish(DirSlot* __restrict__ cache, uint64_t mask, uint64_t
                             const uint64_t* __restrict__ st) {
     if (threadIdx.x != 0) return;
     if (cnt[0] != st[ST_FINAL]) raise(cnt, kErrInvariant);  // the apply and the serial pass disagree on the live count
-    gens_of(cache, mask)[mask + 1] += n;
+    cache_gens(cache, mask)[mask + 1] += n;
 }
 
 // ---- tombstone compaction -------------------------------------------------------------------------------------------
@@ -511,18 +478,18 @@ __global__ __launch_bounds__(256) void k_rb_move(const DirSlot* __restrict__ src
     bool moved = false;
     if (s <= mask && src[s].state == SLOT_FULL) {
         const DirSlot e = src[s];
-        const unsigned long long stamp = gens_of(src, mask)[s];
+        const unsigned long long stamp = cache_gens(src, mask)[s];
         uint64_t cur = dir_slot(jenkins3(e.tcd, e.n0, e.n1), mask);
         for (uint64_t step = 0; step <= mask && !moved; ++step) {
             uint32_t expect = 0;  // EMPTY (the table was zeroed); keys are distinct, so the first free slot is the place
-            if (__hip_atomic_compare_exchange_strong(word28(dst, cur), &expect, (uint32_t)SLOT_CLAIMING << 8, __ATOMIC_RELAXED,
+            if (__hip_atomic_compare_exchange_strong(slot_word28(dst, cur), &expect, (uint32_t)SLOT_CLAIMING << 8, __ATOMIC_RELAXED,
                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                 uint64_t* w = reinterpret_cast<uint64_t*>(dst + cur);
                 w[0] = e.tcd;
                 w[1] = e.n0;
                 w[2] = e.n1;
                 w[3] = (uint64_t)e.act | ((uint64_t)e.silo << 32) | ((uint64_t)SLOT_FULL << 40);
-                gens_of(dst, mask)[cur] = stamp;
+                cache_gens(dst, mask)[cur] = stamp;
                 if (adaptive) {  // the entry keeps its ETag, timer and access mark (`seen` beside its unchanged stamp)
                     const CacheAdaptive from = cache_adaptive(src, mask), to = cache_adaptive(dst, mask);
                     to.etag[cur] = from.etag[s];
@@ -547,7 +514,7 @@ __global__ void k_rb_begin(uint64_t* __restrict__ st) {
 __global__ void k_rb_finish(const DirSlot* __restrict__ src, DirSlot* __restrict__ dst, uint64_t mask, uint64_t* __restrict__ st,
                             uint64_t* __restrict__ cnt) {
     if (threadIdx.x != 0) return;
-    gens_of(dst, mask)[mask + 1] = gens_of(src, mask)[mask + 1];  // G runs on
+    cache_gens(dst, mask)[mask + 1] = cache_gens(src, mask)[mask + 1];  // G runs on
     if (st[ST_REBUILT] != cnt[0]) raise(cnt, kErrInvariant);
     cnt[0] = st[ST_REBUILT];
     cnt[1] = 0;
@@ -587,18 +554,8 @@ __global__ __launch_bounds__(256) void k_ra_prep(const DirSlot* __restrict__ cac
     uint32_t os = kNone, grp = kNone;
     if (op != OP_IGNORE) {
         const orl_grain_key k = keys[i];
-        const uint32_t h = jenkins3(k.type_code_data, k.n0, k.n1);
-        uint64_t cur = dir_slot(h, mask);
-        for (uint64_t step = 0; step <= mask; ++step) {
-            const uint32_t state = load_state(cache, cur);
-            if (state == SLOT_EMPTY) break;
-            if (state == SLOT_FULL && key_eq(cache, cur, k)) {
-                os = (uint32_t)cur;
-                break;
-            }
-            cur = (cur + 1) & mask;
-        }
-        uint32_t g = fmix32(h) & gmask;
+        os = (uint32_t)find_full<true>(cache, mask, k);  // not found: ~0 truncates to kNone
+        uint32_t g = fmix32(jenkins3(k.type_code_data, k.n0, k.n1)) & gmask;
         for (uint32_t step = 0; step <= gmask; ++step) {
             const uint32_t occ = atomicCAS(&group_tab[g], kNone, i);
             if (occ == kNone) {
@@ -663,7 +620,7 @@ __global__ __launch_bounds__(256) void k_ra_snapshot(const DirSlot* __restrict__
         }
     }
     if (n_add == 0 || s > mask) return;
-    skey[s] = load_state(cache, s) == SLOT_FULL ? gens_of(cache, mask)[s] : ~0ull;
+    skey[s] = slot_state(cache, s) == SLOT_FULL ? cache_gens(cache, mask)[s] : ~0ull;
 }
 
 // prevpos of every entry that takes a step, and nxt of the candidates the response names (each by one entry).
@@ -819,7 +776,7 @@ __global__ __launch_bounds__(256) void k_ra_apply(DirSlot* __restrict__ cache, u
                 if (evicted)
                     gone = true;
                 else
-                    cache_mark_fresh_slot(cache, mask, os, gens_of(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
+                    cache_mark_fresh_slot(cache, mask, os, cache_gens(cache, mask)[mask + 1] + i + 1ull, now, max_ttl, growth);
             }
             if (gone) cache[os].state = SLOT_TOMB;
         }
@@ -837,7 +794,7 @@ __global__ void k_ra_finish(DirSlot* __restrict__ cache, uint64_t mask, uint64_t
                             const uint64_t* __restrict__ st, uint32_t serial, uint64_t* __restrict__ d_counts) {
     if (threadIdx.x != 0) return;
     if (serial && st[ST_ADDS] != 0 && cnt[0] != st[ST_FINAL]) raise(cnt, kErrInvariant);  // as k_ev_finish
-    gens_of(cache, mask)[mask + 1] += n;
+    cache_gens(cache, mask)[mask + 1] += n;
     if (d_counts) {
         const uint64_t a = st[ST_ADDS], r = st[ST_REMOVES], f = st[ST_FRESHES];
         d_counts[0] = a;

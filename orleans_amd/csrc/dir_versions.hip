@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dir_table_dev.h"
 #include "dir_versions.h"
 
 namespace orl {
@@ -20,8 +21,6 @@ namespace {
 constexpr uint32_t kLumKinds = 5;           // ORL_LUM_UNCHANGED .. ORL_LUM_UNSUPPORTED
 constexpr uint32_t kLumNone = 0xFFu;        // a lane past the batch's end: no kind
 constexpr size_t kLumChunk = (size_t)1 << 30;  // requests per launch (2^22 blocks of 256)
-
-__device__ __forceinline__ bool mask_bit(const uint32_t* m, uint32_t i) { return (m[i >> 5] >> (i & 31u)) & 1u; }
 
 // One lane per request.  The walk reads a slot's last 8 bytes first (act | silo << 32 | state << 40: the state decides
 // whether the 24-B key is compared at all, and a match needs nothing more from the slot), then the key of FULL slots.

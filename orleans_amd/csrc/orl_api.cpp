@@ -2283,7 +2283,7 @@ int cache_config(orl_ctx* c, uint64_t capacity, bool adaptive) {
     c->cache_slots = 0;
     c->cache_adaptive = false;
     const uint64_t slots = next_pow2(2 * capacity);
-    // the table, then one u64 LRU generation per slot and the generation base (route_kernels.hip cache_gens), then, in
+    // the table, then one u64 LRU generation per slot and the generation base (dir_table_dev.h cache_gens), then, in
     // adaptive mode, the per-slot adaptive state (orl_internal.h CacheAdaptive)
     const size_t bytes = cache_table_bytes(slots, adaptive);
     ORL_HIP(c, hipMalloc((void**)&c->d_cache, bytes));

@@ -1,4 +1,4 @@
-// orl_internal.h — layouts shared by the host side (orl_api.cpp) and the CDNA4 kernels (route_kernels.hip).
+// orl_internal.h — layouts shared by the host side (orl_api.cpp) and the CDNA4 kernels (route_kernels.hip, dir_mutate.hip).
 //
 // Nothing here is part of the public ABI (include/orleans_route.h is).
 #pragma once
@@ -311,7 +311,7 @@ struct DirTags {
     int32_t* winner = nullptr;
 };
 
-// ---- kernel launchers (route_kernels.hip) ---------------------------------------------------------
+// ---- kernel launchers (route_kernels.hip; directory mutation: dir_mutate.hip) ----------------------
 // All return hipError_t as int; they only enqueue on `stream`.
 // KeyExt (string-key) directory slot, 48 B (round 5): the UniqueKey's 24 B, its KeyExt uniform hash, the activation
 // handle, where the KeyExt bytes lie in the context's KeyExt blob, the silo and the slot state (SLOT_*).  Open addressing
@@ -428,7 +428,7 @@ int launch_fanout_expand(const uint64_t* d_csr_off, const uint32_t* d_csr_tgt, c
                          const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub, uint64_t follower_tcd, uint32_t opts,
                          uint64_t* d_pub_offsets, orl_msg_hdr* d_out, uint64_t* n_out, uint64_t cap, const Scratch& s,
                          void* stream);
-// Directory mutation on the device (dir kernels in route_kernels.hip).  d_claim: one u32 per table slot, all
+// Directory mutation on the device (dir_mutate.hip; the split stays in route_kernels.hip).  d_claim: one u32 per table slot, all
 // 0xFFFFFFFF between calls; d_cnt: {entries, tombstones} device counters; d_slot: one u32 per batch message.
 int launch_dir_insert(const RouteParams* d_params, DirSlot* d_dir, uint64_t dir_mask, uint32_t* d_claim, uint64_t* d_cnt,
                       const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n, uint32_t n_act,
@@ -541,7 +541,7 @@ int ctx_route_received(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t
                        const uint32_t* d_in_act, void* stream);
 // KeyExt grains of a routed batch (orl_route_keyext_device): each message k_route left ORL_ST_KEYEXT_UNRESOLVED gets
 // its owner's lookup in the KeyExt table when the owner is local (HIT, or placement on a miss) or ORL_ST_REMOTE_OWNER.
-// KeyExt registration on the device (k_kx_ins_probe / resolve / commit); d_state = {string bytes used, entries, tombstones,
+// KeyExt registration on the device (dir_mutate.hip k_kx_ins_probe / resolve / commit); d_state = {string bytes used, entries, tombstones,
 // error}; d_slot: n words of scratch.
 int launch_keyext_insert(const RouteParams* d_params, ExtSlot* d_table, uint64_t mask, uint32_t* d_claim, uint8_t* d_tblob,
                          uint64_t tblob_cap, const orl_grain_key* d_keys, const orl_ext_ref* d_ext, const uint8_t* d_blob,
