@@ -815,6 +815,93 @@ int orl_route_received_device(orl_ctx* ctx, const void* d_in, uint32_t fmt, size
  * orl_route_batch_device's order / bucket_offsets for these handles (ORL_NO_ACT and handles >= n_act: bucket n_act). */
 int orl_bucket_device(orl_ctx* ctx, const uint32_t* d_act, size_t n, uint32_t* d_order, uint32_t* d_bucket_offsets, void* stream);
 
+/* ---- admission: what the target activation does with each message of a bucketed batch --------------------
+ * After stage 4 the reference decides per message, under the activation's lock, whether it runs now, waits, is rejected,
+ * forwarded, dropped or handed to the response path: IncomingMessageAgent.ReceiveMessage (IncomingMessageAgent.cs:144-181)
+ * and its closure Dispatcher.ReceiveMessage -> ReceiveRequest -> ActivationMayAcceptRequest / CanInterleave ->
+ * HandleIncomingRequest or EnqueueRequest (Dispatcher.cs:78-204, 265-338, 375-427).  orl_admit_device makes that decision
+ * for a whole batch: the messages of one activation in arrival order, each seeing the state the earlier ones left, no
+ * request completing inside the batch (completion, ResetRunning and the message pump stay with the host, which edits the
+ * state table between batches).
+ *
+ * orl_act_state, one per activation handle (n_act entries in device memory, caller-owned, updated in place):
+ *   state        ORL_ACT_* in the order of ActivationState (ActivationState.cs:26-48); ORL_ACT_ABSENT = no ActivationData
+ *                (Catalog.cs:459-466); larger values behave as ABSENT
+ *   flags        ORL_ACTF_REENTRANT (Catalog.IsReentrantGrain), ORL_ACTF_RUNNING_SET (Running != null), ORL_ACTF_RUNNING_RO
+ *                (Running.IsReadOnly), ORL_ACTF_STATELESS (selects hard_stateless, ActivationData.cs:563-575)
+ *   num_running  numRunning (ActivationData.cs:406-422)
+ *   in_flight    InFlightCount (incremented by the InvokeWorkItem constructor, InvokeWorkItem.cs:46)
+ *   waiting      WaitingCount
+ * d_mflags[i]: bits 0-1 Message.Directions (Request 0, Response 1, OneWay 2; Message.cs:124-129), ORL_MF_READ_ONLY,
+ *   ORL_MF_ALWAYS_INTERLEAVE, ORL_MF_EXPIRED.
+ * orl_admit_limits: MaxEnqueuedRequests' hard limit for ordinary and for stateless-worker activations; <= 0 = none (the
+ *   soft limit only logs).
+ *
+ * Message i with handle a < n_act, L = the limit a's flags select, c = in_flight + waiting as the earlier messages left it:
+ *   1. state == VALID && L > 0 && c > L                    ORL_ADM_OVERLOADED, every direction (IncomingMessageAgent.cs:153-161,
+ *                                                          ActivationData.CheckOverloaded :522-561; the host sends a rejection
+ *                                                          only for a Request, Dispatcher.RejectMessage :206-225)
+ *   2. expired                                             ORL_ADM_EXPIRED       (Dispatcher.cs:82-88)
+ *   3. ABSENT                                              ORL_ADM_NONEXISTENT   (:132-197)
+ *   4. Response                                            ORL_ADM_INVALID on an INVALID activation (:245-251), else
+ *                                                          ORL_ADM_RESPONSE; no state change
+ *   5. Request / OneWay on INVALID                         ORL_ADM_INVALID       (ProcessRequestToInvalidActivation :269-276)
+ *   6. state == VALID && (num_running == 0 || REENTRANT || always-interleave || !RUNNING_SET || (RUNNING_RO && read-only))
+ *                                                          ORL_ADM_RUN (:316-338): num_running++, in_flight++, and when
+ *                                                          !RUNNING_SET it is set with RUNNING_RO from the message
+ *                                                          (RecordRunning keeps the first, ActivationData.cs:411-422)
+ *   7. otherwise EnqueueRequest (:401-427)                 ORL_ADM_OVERLOADED when L > 0 && c + (state == VALID) > L, else
+ *                                                          ORL_ADM_ENQUEUE and waiting++
+ * Handles >= n_act (ORL_NO_ACT included; stage 4's bucket n_act) get ORL_ADM_UNRESOLVED and read no state: new placements,
+ * which the host activates.  Counters are 32-bit and must not wrap; the comparisons are made in 64 bits; n < 2^32.
+ *
+ * orl_admit_device runs on `stream` after the bucketing call that wrote d_order / d_bucket_offsets for d_act (exactly
+ * those arrays; the device finds a position's bucket in d_bucket_offsets and does not read d_act again), without a
+ * device-wide sync or a copy to the host.  d_disp[i] (message order) gets message i's code;
+ * d_counts (optional, device u64[8]) is zeroed on the stream and then receives the number of messages per code.  Scratch
+ * is allocated on the first call, sized by max_batch (n > max_batch: ORL_E_CAPACITY); n == 0 is valid; a host-only context
+ * answers ORL_E_STATE. */
+#define ORL_ACT_CREATE 0u
+#define ORL_ACT_ACTIVATING 1u
+#define ORL_ACT_VALID 2u
+#define ORL_ACT_DEACTIVATING 3u
+#define ORL_ACT_INVALID 4u
+#define ORL_ACT_ABSENT 5u
+#define ORL_ACTF_REENTRANT 0x01u
+#define ORL_ACTF_RUNNING_SET 0x02u
+#define ORL_ACTF_RUNNING_RO 0x04u
+#define ORL_ACTF_STATELESS 0x08u
+#define ORL_MF_DIR_MASK 0x03u
+#define ORL_MF_REQUEST 0u
+#define ORL_MF_RESPONSE 1u
+#define ORL_MF_ONE_WAY 2u
+#define ORL_MF_READ_ONLY 0x04u
+#define ORL_MF_ALWAYS_INTERLEAVE 0x08u
+#define ORL_MF_EXPIRED 0x10u
+#define ORL_ADM_RUN 0u
+#define ORL_ADM_ENQUEUE 1u
+#define ORL_ADM_RESPONSE 2u
+#define ORL_ADM_OVERLOADED 3u
+#define ORL_ADM_INVALID 4u
+#define ORL_ADM_NONEXISTENT 5u
+#define ORL_ADM_EXPIRED 6u
+#define ORL_ADM_UNRESOLVED 7u
+typedef struct orl_act_state {
+    uint8_t state;
+    uint8_t flags;
+    uint16_t reserved; /* zero */
+    uint32_t num_running;
+    uint32_t in_flight;
+    uint32_t waiting;
+} orl_act_state;
+typedef struct orl_admit_limits {
+    int32_t hard;
+    int32_t hard_stateless;
+} orl_admit_limits;
+int orl_admit_device(orl_ctx* ctx, const uint32_t* d_act, const uint8_t* d_mflags, size_t n, const uint32_t* d_order,
+                     const uint32_t* d_bucket_offsets, orl_act_state* d_state, const orl_admit_limits* limits,
+                     uint8_t* d_disp, uint64_t* d_counts, void* stream);
+
 /* ---- device memory for callers without a GPU runtime (the P/Invoke silo) ---------------------------------
  * A .NET host drives the *_device entry points through these: allocate HBM on the context's device, copy host arrays
  * in and out on a stream (a NULL stream is the context's own), wait.  orl_host_register page-locks a caller array once

@@ -68,6 +68,14 @@ MERGE_INSERTED, MERGE_KEPT, MERGE_REPLACED, MERGE_SAME, MERGE_DUPLICATE, MERGE_U
 DIR_NO_ETAG = -1  # GrainInfo.NO_ETAG: no entry (version tags are >= 0)
 LUM_UNCHANGED, LUM_ABSENT, LUM_UPDATED, LUM_UPDATED_EMPTY, LUM_UNSUPPORTED = 0, 1, 2, 3, 4  # orl_dir_lookup_many_* kinds
 
+# orl_admit_device: orl_act_state.state / .flags, the d_mflags bits, the disposition codes
+ACT_CREATE, ACT_ACTIVATING, ACT_VALID, ACT_DEACTIVATING, ACT_INVALID, ACT_ABSENT = 0, 1, 2, 3, 4, 5
+ACTF_REENTRANT, ACTF_RUNNING_SET, ACTF_RUNNING_RO, ACTF_STATELESS = 0x01, 0x02, 0x04, 0x08
+MF_DIR_MASK, MF_REQUEST, MF_RESPONSE, MF_ONE_WAY = 0x03, 0, 1, 2
+MF_READ_ONLY, MF_ALWAYS_INTERLEAVE, MF_EXPIRED = 0x04, 0x08, 0x10
+(ADM_RUN, ADM_ENQUEUE, ADM_RESPONSE, ADM_OVERLOADED, ADM_INVALID, ADM_NONEXISTENT, ADM_EXPIRED,
+ ADM_UNRESOLVED) = range(8)
+
 Q_PROBE_FORM, Q_FULL_UPLOADS, Q_SLOT_PATCHES, Q_DEVICE, Q_N_ACT, Q_MAX_BATCH, Q_RANK_MODE = 1, 2, 3, 4, 5, 6, 7
 Q_WIRE_DIGEST = 8
 Q_PART_ERROR = 9
@@ -88,6 +96,10 @@ EXT_REF_DTYPE = np.dtype([("off", "<u4"), ("len", "<u4")])  # orl_ext_ref: a Key
 MSG_DTYPE = np.dtype([("tcd", "<u8"), ("n0", "<u8"), ("n1", "<u8"), ("sending_silo", "u1"), ("category", "u1"),
                       ("flags", "u1"), ("target_silo", "u1"), ("aux", "<u4")])
 assert KEY_DTYPE.itemsize == 24 and MSG_DTYPE.itemsize == 32
+# orl_act_state: one per activation handle, read and updated by orl_admit_device
+ACT_STATE_DTYPE = np.dtype([("state", "u1"), ("flags", "u1"), ("reserved", "<u2"), ("num_running", "<u4"),
+                            ("in_flight", "<u4"), ("waiting", "<u4")])
+assert ACT_STATE_DTYPE.itemsize == 16
 
 
 class orl_config(C.Structure):
@@ -131,6 +143,10 @@ class orl_cache_stats(C.Structure):
 
 class orl_cache_sweep(C.Structure):
     _fields_ = [("d_keys", C.c_void_p), ("d_etags", C.c_void_p), ("d_owner_offsets", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+class orl_admit_limits(C.Structure):
+    _fields_ = [("hard", C.c_int32), ("hard_stateless", C.c_int32)]
 
 
 class orl_node_chunk_plan(C.Structure):
@@ -245,6 +261,7 @@ _SIGS = {
     "orl_sync": (C.c_int, [_P]),
     "orl_ctx_query": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64)]),
     "orl_bucket_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
+    "orl_admit_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, C.POINTER(orl_admit_limits), _P, _P, _P]),
     "orl_ctx_set_rank_mode": (C.c_int, [_P, C.c_uint32]),
     "orl_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "orl_device_free": (C.c_int, [_P, _P]),

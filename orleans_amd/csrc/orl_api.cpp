@@ -19,6 +19,7 @@
 
 #include "orl_internal.h"
 #include "cache_adaptive.h"
+#include "admit.h"
 #include "dir_versions.h"
 #include "cache_evict.h"
 
@@ -267,6 +268,7 @@ struct orl_ctx {
     int64_t cache_initial_ttl = 0, cache_max_ttl = 0;  // initialExpirationTimer, maxExpirationTimer (.NET ticks)
     double cache_growth = 0;                           // exponentialTimerGrowth
     int64_t cache_now = 0;                             // the last now_ticks a call gave (the plain add's DateTime.UtcNow)
+    AdmitScratch adm;                                  // orl_admit_device's scratch (admit.hip), allocated by its first call
     CacheSweepScratch csw;                             // the maintainer's scratch and output (cache_adaptive.hip)
     // stateless-worker grains (StatelessWorkerDirector.cs:35-80): the listed types with their MaxLocal, and the local
     // catalog's host mirror (SwSlot), uploaded whole when the host changed it (sw_dirty).  orl_sw_set_busy_device makes
@@ -787,7 +789,7 @@ int ensure_staging(orl_ctx* c, size_t in_bytes, size_t out_words) {
 
 void free_device(orl_ctx* c) {
     auto f = [](void* p) { if (p) (void)hipFree(p); };
-    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_vtag); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); cache_sweep_free(&c->csw); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
+    f(c->d_table); f(c->d_probe); f(c->d_probe8); f(c->d_probe_bad); f(c->d_params); f(c->d_rank_of_silo); f(c->d_claim); f(c->d_vtag); f(c->d_dirstate); f(c->d_dslot); f(c->d_vr_hash); f(c->d_vr_silo); f(c->d_silo_hash); f(c->d_silo_known); f(c->d_dflag); f(c->d_cache); f(c->d_cache2); cache_evict_free(&c->cev); cache_sweep_free(&c->csw); admit_free(&c->adm); f(c->d_cclaim); f(c->d_cstate); f(c->d_silo_tab); f(c->d_decode_flag); f(c->d_silo_words); f(c->d_gt); f(c->d_gt_blob); f(c->d_stamp_sizes); f(c->d_stamp_temp); f(c->d_patch_data); f(c->d_csr_off); f(c->d_csr_tgt); f(c->d_ext_table); f(c->d_ext_blob); f(c->d_ext_claim); f(c->d_ext_state); f(c->d_sw);
     f(c->s.pairs_a); f(c->s.pairs_b); f(c->s.idx_a); f(c->s.sorted_keys); f(c->s.tile_hist); f(c->s.tile_cnt); f(c->s.scan_sums); f(c->s.digits); f(c->s.col_sums); f(c->s.col_tot); f(c->s.seg_hist); f(c->s.seg_carry); f(c->s.seg_meta); f(c->s.seg_lb); f(c->s.seg_lbctl); f(c->s.bstart); f(c->s.sstart); f(c->s.gap_q); f(c->s.hot); f(c->s.hot_rows); f(c->s.hot_bmax); f(c->s.pick_word); f(c->s.fan_blk); f(c->s.lsd_hot);
     for (auto& L : c->s.lb) {
         f(L.state);
@@ -3074,6 +3076,24 @@ int orl_bucket_device(orl_ctx* c, const uint32_t* d_act, size_t n, uint32_t* d_o
     if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
     int e = launch_bucket_acts(d_act, n, c->cfg.n_act, d_order, d_off, c->s, stream ? stream : c->stream);
     if (e) return hipfail(c, (hipError_t)e, "bucket launch");
+    return ORL_OK;
+}
+
+int orl_admit_device(orl_ctx* c, const uint32_t* d_act, const uint8_t* d_mflags, size_t n, const uint32_t* d_order,
+                     const uint32_t* d_off, orl_act_state* d_state, const orl_admit_limits* limits, uint8_t* d_disp,
+                     uint64_t* d_counts, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!limits) return fail(c, ORL_E_INVALID, "null limits");
+    if (n && (!d_act || !d_mflags || !d_order || !d_off || !d_state || !d_disp)) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (!c->adm.base) {  // a synchronising allocation, once
+        ORL_HIP(c, hipSetDevice(c->cfg.device));
+        if (int e = admit_alloc(&c->adm, c->s.max_batch)) return hipfail(c, (hipError_t)e, "admission scratch");
+    }
+    int e = launch_admit(d_mflags, n, c->cfg.n_act, d_order, d_off, d_state, *limits, d_disp, d_counts, c->adm,
+                         stream ? stream : c->stream);
+    if (e) return hipfail(c, (hipError_t)e, "admission launch");
     return ORL_OK;
 }
 

@@ -852,6 +852,16 @@ class GrainDirectoryEngine:
         """Stage 4 alone over routed activation handles (the receiving silo's side of hop 2)."""
         self._ck(self._lib.orl_bucket_device(self._ctx, ptr(d_act), int(n), ptr(d_order), ptr(d_offsets), ptr(stream)))
 
+    def admit_device(self, d_act, d_mflags, n: int, d_order, d_offsets, d_state, d_disp, hard: int = 0,
+                     hard_stateless: int = 0, d_counts=None, stream=None) -> None:
+        """What each message's activation does with it (IncomingMessageAgent.ReceiveMessage / Dispatcher.ReceiveMessage),
+        on `stream` after the bucketing call that wrote d_order / d_offsets for d_act: d_disp[i] gets an ADM_* code in
+        message order and d_state (n_act entries of ACT_STATE_DTYPE) is updated in place.  d_mflags: one byte per message
+        (MF_*).  hard / hard_stateless: MaxEnqueuedRequests' hard limits, <= 0 for none.  d_counts: 8 uint64 (written)."""
+        lim = L.orl_admit_limits(int(hard), int(hard_stateless))
+        self._ck(self._lib.orl_admit_device(self._ctx, ptr(d_act), ptr(d_mflags), int(n), ptr(d_order), ptr(d_offsets),
+                                            ptr(d_state), C.byref(lim), ptr(d_disp), ptr(d_counts), ptr(stream)))
+
     def copy_to_host(self, h_dst: np.ndarray, d_src, nbytes: Optional[int] = None, stream=None) -> np.ndarray:
         """orl_copy_to_host + orl_stream_sync (the P/Invoke caller's way to read device outputs)."""
         nb = h_dst.nbytes if nbytes is None else int(nbytes)
