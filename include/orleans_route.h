@@ -802,9 +802,12 @@ int orl_partition_cached_device(orl_ctx* ctx, const orl_msg_hdr* d_in, size_t n,
                                 uint32_t* d_act_out, uint64_t* d_counts, uint32_t* d_status, void* stream);
 /* Stages 1-3 of received hop-1 records (fmt 8 / 16 / 32) with their act lane: a record whose lane entry is not ORL_NO_ACT
  * was addressed by its sender's cache.  When this context holds the grain's directory partition, the record is routed by
- * the directory and keeps HIT | ORL_RF_CACHED only if the directory holds that handle on that silo; otherwise it gets the
- * directory's word | ORL_RF_CACHE_STALE (the receiving silo's NonExistentActivation forward, Dispatcher.cs:138-182).  When
- * it does not, the record gets HIT | ORL_RF_CACHED with its target silo as host and that handle, without a probe.  The
+ * the directory and keeps HIT | ORL_RF_CACHED only if the directory holds that handle on that silo and the silo is functional
+ * in this context's silo table; otherwise it gets the directory's word | ORL_RF_CACHE_STALE (the receiving silo's
+ * NonExistentActivation forward, Dispatcher.cs:138-182).  When it does not, the record gets HIT | ORL_RF_CACHED with its
+ * target silo as host and that handle, without a probe — under this context's `functional` mask too (IsValidSilo,
+ * LocalGrainDirectory.cs:711-717): a target silo that is not functional here gives ORL_ST_REMOTE_OWNER with ORL_NO_ACT, the
+ * FullLookup path.  This context's own directory cache is neither consulted nor stamped for an addressed record.  The
  * others are routed as orl_route_*_device do.  No stage 4 (ORL_OPT_NO_BUCKETS implied; orl_bucket_device follows over the
  * hosted set). */
 int orl_route_received_device(orl_ctx* ctx, const void* d_in, uint32_t fmt, size_t n, uint32_t opts, const uint32_t* d_in_act,

@@ -473,8 +473,12 @@ class GrainDirectoryEngine:
                                                        ptr(d_counts), ptr(d_status), ptr(stream)))
 
     def route_received_device(self, d_recs, fmt: int, n: int, d_in_act, d_route, d_act, stream=None, opts: int = 0) -> None:
-        """Stages 1-3 of received hop-1 records with their act lane (orl_route_received_device): records addressed by the
-        sender's cache become HIT | CACHED without a probe."""
+        """Stages 1-3 of received hop-1 records with their act lane (orl_route_received_device).  A record its sender's cache
+        addressed (lane entry not NO_ACT): where this context holds the grain's directory partition the directory routes it,
+        and it keeps HIT | CACHED only if the directory holds that handle on that silo and the silo is functional here —
+        otherwise the directory's word | CACHE_STALE; where it does not, the record becomes HIT | CACHED on its target silo
+        without a probe if that silo is functional here, else REMOTE_OWNER with NO_ACT.  The others are routed as
+        address_*_device route them.  No stage 4."""
         self._ck(self._lib.orl_route_received_device(self._ctx, ptr(d_recs), int(fmt), int(n), int(opts), ptr(d_in_act),
                                                      ptr(d_route), ptr(d_act), ptr(stream)))
 

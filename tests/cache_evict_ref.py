@@ -237,15 +237,17 @@ class World:
     """The cluster of the directory-cache tests (8 silos, two of them local, one not functional), its CPU oracle and a
     grain population; route batches that look every grain up at least once."""
 
-    def __init__(self, n_grains, n_act=60_000):
+    def __init__(self, n_grains, n_act=60_000, running=None):
+        """running (optional): LocalGrainDirectory.Running per silo (tests/hop1_ref.py stops one local silo); all by default."""
         from oracle import cpu_ref
         from orleans_amd import workloads as W
         self.W = W
         self.cl = W.default_cluster()
         self.local = [1, 1, 0, 0, 0, 0, 0, 0]
         self.functional = [1, 1, 1, 1, 1, 1, 0, 1]
+        self.running = [1] * 8 if running is None else list(running)
         self.n_grains, self.n_act = n_grains, n_act
-        self.o = cpu_ref.Oracle(8, functional=self.functional, local=self.local)
+        self.o = cpu_ref.Oracle(8, running=self.running, functional=self.functional, local=self.local)
         for s in range(8):
             self.o.add_server(s, int(self.cl.hashes[s]))
         self.keys, _, self.owner, _ = W.grain_population(self.cl, n_grains)
