@@ -824,8 +824,8 @@ int orl_bucket_device(orl_ctx* ctx, const uint32_t* d_act, size_t n, uint32_t* d
  * and its closure Dispatcher.ReceiveMessage -> ReceiveRequest -> ActivationMayAcceptRequest / CanInterleave ->
  * HandleIncomingRequest or EnqueueRequest (Dispatcher.cs:78-204, 265-338, 375-427).  orl_admit_device makes that decision
  * for a whole batch: the messages of one activation in arrival order, each seeing the state the earlier ones left, no
- * request completing inside the batch (completion, ResetRunning and the message pump stay with the host, which edits the
- * state table between batches).
+ * request completing inside the batch (completion, ResetRunning and the message pump run between batches: on the device
+ * through orl_waitq_append_device / orl_complete_device below, or by a host that edits the state table itself).
  *
  * orl_act_state, one per activation handle (n_act entries in device memory, caller-owned, updated in place):
  *   state        ORL_ACT_* in the order of ActivationState (ActivationState.cs:26-48); ORL_ACT_ABSENT = no ActivationData
@@ -904,6 +904,91 @@ typedef struct orl_admit_limits {
 int orl_admit_device(orl_ctx* ctx, const uint32_t* d_act, const uint8_t* d_mflags, size_t n, const uint32_t* d_order,
                      const uint32_t* d_bucket_offsets, orl_act_state* d_state, const orl_admit_limits* limits,
                      uint8_t* d_disp, uint64_t* d_counts, void* stream);
+
+/* ---- waiting queues: the append after admission, request completion and the message pump -----------------
+ * The other half of admission.  A message that got ORL_ADM_ENQUEUE waits on its activation's list
+ * (ActivationData.EnqueueMessage, ActivationData.cs:487-514); when a request completes, the reference resets Running
+ * (ActivationData.ResetRunning, :424-442), decrements InFlightCount (InvokeWorkItem.cs:70,79) and runs the message pump
+ * (Dispatcher.RunMessagePump, Dispatcher.cs:633-685), which takes waiting messages from the head while
+ * ActivationMayAcceptRequest (:316-338) holds.  With these calls the state table never leaves the device between batches.
+ *
+ * Tokens: the caller names every message with a uint32_t (d_tok[i], message order); ORL_TOK_NONE and ORL_TOK_DRAIN are
+ * reserved.
+ *
+ * orl_waitq (opaque; one per context, for the context's n_act and `capacity` records) holds
+ *   the store        every waiting record, sorted by activation handle, FIFO inside an activation, as a CSR: off[n_act + 1],
+ *                    and per record tok, mflags (the ORL_MF_* byte) and act.  Double-buffered: every mutating call streams
+ *                    the current buffers into the other ones;
+ *   running_tok      [n_act] the token of the activation's Running message, ORL_TOK_NONE when Running == null.  At every
+ *                    call boundary running_tok[a] != ORL_TOK_NONE <=> ORL_ACTF_RUNNING_SET; a host that edits RUNNING_SET
+ *                    itself writes running_tok too (orl_waitq_view.d_running_tok);
+ *   the out list     of the last orl_complete_device: out_tok, out_act, out_mflags, out_kind (ORL_WQ_RUN / ORL_WQ_DRAINED)
+ *                    and a device u64 length; ascending activation handle, FIFO inside an activation; queue-owned and
+ *                    `capacity` long, so it cannot overflow.
+ * orl_waitq_view_get gives the device pointers of the CURRENT buffers (stale after the next append / complete).
+ *
+ * orl_waitq_append_device runs on `stream` right after orl_admit_device and reads that call's d_disp and the bucketing
+ * call's d_order / d_bucket_offsets:
+ *   every message with ORL_ADM_ENQUEUE is appended to its activation's FIFO in arrival order (EnqueueMessage :487-514);
+ *   for every activation with running_tok == ORL_TOK_NONE whose bucket holds an ORL_ADM_RUN message, running_tok becomes
+ *   the token of the bucket's first RUN message in arrival order (RecordRunning keeps the first, :411-422);
+ *   orl_act_state is not touched (admission already counted); bucket n_act (unresolved) contributes nothing.
+ *
+ * orl_complete_device takes m records (d_cact[j], d_ctok[j]) and the d_corder / d_cbucket_offsets that orl_bucket_device
+ * wrote for d_cact on the same stream (the buckets are those of d_cact; the device reads the offsets and not d_corder).
+ * A record is a completion (an ordinary token), a pump request (ORL_TOK_NONE; the reference pumps after an activation
+ * finishes activating, Catalog.cs:1093) or a drain (ORL_TOK_DRAIN: DequeueAllWaitingMessages, ActivationData.cs:590-599,
+ * as called before ProcessRequestsToInvalidActivation).  Handles >= n_act are ignored and counted.  For each activation a
+ * with at least one record, k = its completions and r = "one of them carries running_tok[a], which is not ORL_TOK_NONE":
+ *   1. in_flight -= k (InvokeWorkItem.cs:70,79), num_running -= k (ResetRunning); both saturate at 0, and the activation is
+ *      then counted as an underflow (a caller error, never a wrap)
+ *   2. if r: RUNNING_SET | RUNNING_RO cleared, running_tok = ORL_TOK_NONE (ActivationData.cs:438-441); a completion whose
+ *      token is not Running's leaves Running as it is
+ *   3. with a drain record: every waiting record goes to the out list as ORL_WQ_DRAINED, waiting = 0, no pump
+ *   4. otherwise, iff state == ORL_ACT_VALID (Dispatcher.cs:669), the pump: it takes waiting records from the head while
+ *      rule 6 of admission holds (Dispatcher.cs:316-338, 672-684: num_running == 0 || REENTRANT || always-interleave ||
+ *      !RUNNING_SET || (RUNNING_RO && read-only)) and stops at the first that fails.  Each record taken: waiting--,
+ *      num_running++, in_flight++, out list ORL_WQ_RUN; one taken while RUNNING_SET is clear becomes Running (the bits
+ *      and running_tok).
+ * Order inside a batch: "the reference called in batch order" with one fixed choice: an activation's completions are
+ * applied with Running's own completion first, the others in any order, each followed by RunMessagePump.  That equals
+ * "apply all completions, then pump once" (DESIGN §17 shows why the choice is a real one).
+ * d_counts (optional, device u64[8], zeroed on the stream): completions applied, pump requests, drain requests, records
+ * with a handle >= n_act, underflowing activations, records run, records drained, records still waiting.
+ *
+ * Capacity: the library keeps a host-side upper bound of the store's length (+= n on append, never lowered by guesswork).
+ * When bound + n > capacity the append first refreshes the bound from the device's true length (one 8-byte copy and a
+ * synchronise of `stream`, on this path only); if it is still over, ORL_E_CAPACITY, nothing launched, nothing changed.
+ * Otherwise no call here synchronises or copies to the host.  A host-only context answers ORL_E_STATE; n or m above
+ * max_batch ORL_E_CAPACITY; n == 0 and m == 0 are valid (m == 0 leaves an empty out list).  capacity < 2^32.
+ * Left out: expiry of waiting messages, becameIdle and the activation collector, RunOnInactive, the host's forwarding of
+ * drained messages, the queues inside orl_node_*. */
+#define ORL_TOK_NONE 0xFFFFFFFFu
+#define ORL_TOK_DRAIN 0xFFFFFFFEu
+#define ORL_WQ_RUN 0u
+#define ORL_WQ_DRAINED 1u
+typedef struct orl_waitq orl_waitq;
+typedef struct orl_waitq_view { /* device pointers of the CURRENT buffers; stale after the next append / complete */
+    const uint32_t* d_off;
+    const uint32_t* d_tok;
+    const uint32_t* d_act;
+    const uint8_t* d_mflags;
+    uint32_t* d_running_tok;
+    const uint32_t* d_out_tok;
+    const uint32_t* d_out_act;
+    const uint8_t* d_out_mflags;
+    const uint8_t* d_out_kind;
+    const uint64_t* d_out_n;
+    const uint64_t* d_waiting_n;
+} orl_waitq_view;
+int orl_waitq_create(orl_ctx* ctx, uint64_t capacity, orl_waitq** out);
+int orl_waitq_destroy(orl_ctx* ctx, orl_waitq* q);
+int orl_waitq_view_get(orl_ctx* ctx, orl_waitq* q, orl_waitq_view* out);
+int orl_waitq_append_device(orl_ctx* ctx, orl_waitq* q, const uint32_t* d_tok, const uint8_t* d_mflags, size_t n,
+                            const uint32_t* d_order, const uint32_t* d_bucket_offsets, const uint8_t* d_disp, void* stream);
+int orl_complete_device(orl_ctx* ctx, orl_waitq* q, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
+                        const uint32_t* d_corder, const uint32_t* d_cbucket_offsets, orl_act_state* d_state,
+                        uint64_t* d_counts, void* stream);
 
 /* ---- device memory for callers without a GPU runtime (the P/Invoke silo) ---------------------------------
  * A .NET host drives the *_device entry points through these: allocate HBM on the context's device, copy host arrays

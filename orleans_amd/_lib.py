@@ -75,6 +75,11 @@ MF_DIR_MASK, MF_REQUEST, MF_RESPONSE, MF_ONE_WAY = 0x03, 0, 1, 2
 MF_READ_ONLY, MF_ALWAYS_INTERLEAVE, MF_EXPIRED = 0x04, 0x08, 0x10
 (ADM_RUN, ADM_ENQUEUE, ADM_RESPONSE, ADM_OVERLOADED, ADM_INVALID, ADM_NONEXISTENT, ADM_EXPIRED,
  ADM_UNRESOLVED) = range(8)
+# orl_waitq: the reserved tokens, the out list's kinds, the order of orl_complete_device's d_counts
+TOK_NONE, TOK_DRAIN = 0xFFFFFFFF, 0xFFFFFFFE
+WQ_RUN, WQ_DRAINED = 0, 1
+(CMP_COMPLETIONS, CMP_PUMPS, CMP_DRAINS, CMP_IGNORED, CMP_UNDERFLOWS, CMP_RUN, CMP_DRAINED,
+ CMP_WAITING) = range(8)
 
 Q_PROBE_FORM, Q_FULL_UPLOADS, Q_SLOT_PATCHES, Q_DEVICE, Q_N_ACT, Q_MAX_BATCH, Q_RANK_MODE = 1, 2, 3, 4, 5, 6, 7
 Q_WIRE_DIGEST = 8
@@ -147,6 +152,13 @@ class orl_cache_sweep(C.Structure):
 
 class orl_admit_limits(C.Structure):
     _fields_ = [("hard", C.c_int32), ("hard_stateless", C.c_int32)]
+
+
+class orl_waitq_view(C.Structure):
+    _fields_ = [("d_off", C.c_void_p), ("d_tok", C.c_void_p), ("d_act", C.c_void_p), ("d_mflags", C.c_void_p),
+                ("d_running_tok", C.c_void_p), ("d_out_tok", C.c_void_p), ("d_out_act", C.c_void_p),
+                ("d_out_mflags", C.c_void_p), ("d_out_kind", C.c_void_p), ("d_out_n", C.c_void_p),
+                ("d_waiting_n", C.c_void_p)]
 
 
 class orl_node_chunk_plan(C.Structure):
@@ -262,6 +274,11 @@ _SIGS = {
     "orl_ctx_query": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint64)]),
     "orl_bucket_device": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
     "orl_admit_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P, C.POINTER(orl_admit_limits), _P, _P, _P]),
+    "orl_waitq_create": (C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
+    "orl_waitq_destroy": (C.c_int, [_P, _P]),
+    "orl_waitq_view_get": (C.c_int, [_P, _P, C.POINTER(orl_waitq_view)]),
+    "orl_waitq_append_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "orl_complete_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "orl_ctx_set_rank_mode": (C.c_int, [_P, C.c_uint32]),
     "orl_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "orl_device_free": (C.c_int, [_P, _P]),

@@ -20,6 +20,7 @@
 #include "orl_internal.h"
 #include "cache_adaptive.h"
 #include "admit.h"
+#include "waitq.h"
 #include "dir_versions.h"
 #include "cache_evict.h"
 
@@ -3094,6 +3095,74 @@ int orl_admit_device(orl_ctx* c, const uint32_t* d_act, const uint8_t* d_mflags,
     int e = launch_admit(d_mflags, n, c->cfg.n_act, d_order, d_off, d_state, *limits, d_disp, d_counts, c->adm,
                          stream ? stream : c->stream);
     if (e) return hipfail(c, (hipError_t)e, "admission launch");
+    return ORL_OK;
+}
+
+// ---- waiting queues (waitq.hip) ---------------------------------------------------------------------------
+int orl_waitq_create(orl_ctx* c, uint64_t capacity, orl_waitq** out) {
+    if (!c || !out) return ORL_E_INVALID;
+    *out = nullptr;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (capacity == 0 || capacity >= 0xFFFFFFFFull) return fail(c, ORL_E_INVALID, "waiting queue capacity must be in 1 .. 2^32 - 2");
+    ORL_HIP(c, hipSetDevice(c->cfg.device));
+    if (int e = waitq_alloc(out, c->cfg.n_act, capacity, c->s.max_batch))
+        return fail(c, ORL_E_NOMEM, "waiting queue of %llu records: %s", (unsigned long long)capacity,
+                    hipGetErrorString((hipError_t)e));
+    return ORL_OK;
+}
+
+int orl_waitq_destroy(orl_ctx* c, orl_waitq* q) {
+    if (!c) return ORL_E_INVALID;
+    if (!q) return ORL_OK;
+    ORL_HIP(c, hipSetDevice(c->cfg.device));
+    waitq_free(q);
+    return ORL_OK;
+}
+
+int orl_waitq_view_get(orl_ctx* c, orl_waitq* q, orl_waitq_view* out) {
+    if (!c || !q || !out) return ORL_E_INVALID;
+    const uint32_t b = q->cur;
+    *out = orl_waitq_view{q->off[b], q->tok[b], q->act[b], q->mflags[b], q->running_tok, q->out_tok,
+                          q->out_act, q->out_mflags, q->out_kind, q->out_n, q->waiting_n};
+    return ORL_OK;
+}
+
+int orl_waitq_append_device(orl_ctx* c, orl_waitq* q, const uint32_t* d_tok, const uint8_t* d_mflags, size_t n,
+                            const uint32_t* d_order, const uint32_t* d_off, const uint8_t* d_disp, void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!q) return fail(c, ORL_E_INVALID, "null waiting queue");
+    if (n && (!d_tok || !d_mflags || !d_order || !d_off || !d_disp)) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (n == 0) return ORL_OK;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (q->bound + n > q->capacity) {  // the bound may overstate: ask the device for the true length, on this path only
+        uint64_t len = 0;
+        ORL_HIP(c, hipMemcpyAsync(&len, q->waiting_n, sizeof(len), hipMemcpyDeviceToHost, st));
+        ORL_HIP(c, hipStreamSynchronize(st));
+        q->bound = len;
+        if (q->bound + n > q->capacity)
+            return fail(c, ORL_E_CAPACITY, "waiting queue: %llu records + a batch of %zu > capacity %llu",
+                        (unsigned long long)len, n, (unsigned long long)q->capacity);
+    }
+    int e = launch_waitq_append(*q, q->bound, d_tok, d_mflags, n, d_order, d_off, d_disp, st);
+    if (e) return hipfail(c, (hipError_t)e, "waiting queue append launch");
+    q->bound += n;
+    q->cur ^= 1u;
+    return ORL_OK;
+}
+
+int orl_complete_device(orl_ctx* c, orl_waitq* q, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
+                        const uint32_t* d_corder, const uint32_t* d_coff, orl_act_state* d_state, uint64_t* d_counts,
+                        void* stream) {
+    if (!c) return ORL_E_INVALID;
+    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (!q) return fail(c, ORL_E_INVALID, "null waiting queue");
+    if (m && (!d_cact || !d_ctok || !d_corder || !d_coff || !d_state)) return fail(c, ORL_E_INVALID, "null device buffer");
+    if (m > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", m, (unsigned long long)c->s.max_batch);
+    int e = launch_waitq_complete(*q, d_cact, d_ctok, m, d_coff, d_state, d_counts, stream ? stream : c->stream);
+    if (e) return hipfail(c, (hipError_t)e, "completion launch");
+    if (m) q->cur ^= 1u;
     return ORL_OK;
 }
 

@@ -18,6 +18,9 @@ hash_batch                     GrainId.GetUniformHashCode (src/Orleans/IDs/Grain
 register_single_activation_    AddSingleActivation with the caller's rand.Next() draw as GrainInfo.VersionTag
 versioned                      (GrainDirectoryPartition.cs:100-114, 270-287)
 lookup_many(_device)           RemoteGrainDirectory.LookUpMany (RemoteGrainDirectory.cs:349-380)
+waitq_append_device            ActivationData.EnqueueMessage / RecordRunning (ActivationData.cs:487-514, 411-422)
+complete_device                ActivationData.ResetRunning (:424-442) + Dispatcher.RunMessagePump
+                               (Dispatcher.cs:633-685)
 =============================  ==================================================================
 
 Error behaviour: API errors raise ``OrleansRouteError`` (the reference throws ArgumentException /
@@ -865,6 +868,41 @@ class GrainDirectoryEngine:
         lim = L.orl_admit_limits(int(hard), int(hard_stateless))
         self._ck(self._lib.orl_admit_device(self._ctx, ptr(d_act), ptr(d_mflags), int(n), ptr(d_order), ptr(d_offsets),
                                             ptr(d_state), C.byref(lim), ptr(d_disp), ptr(d_counts), ptr(stream)))
+
+    def waitq_create(self, capacity: int) -> C.c_void_p:
+        """A waiting-queue object for this context's n_act and `capacity` records: the per-activation waiting lists
+        (ActivationData.waiting, ActivationData.cs:470-514), Running's token per activation and the out list."""
+        q = C.c_void_p()
+        self._ck(self._lib.orl_waitq_create(self._ctx, int(capacity), C.byref(q)))
+        return q
+
+    def waitq_destroy(self, q) -> None:
+        self._ck(self._lib.orl_waitq_destroy(self._ctx, q))
+
+    def waitq_view(self, q) -> "L.orl_waitq_view":
+        """Device pointers of the queue's CURRENT buffers (store, running_tok, out list, the two u64 lengths); stale
+        after the next append / complete."""
+        v = L.orl_waitq_view()
+        self._ck(self._lib.orl_waitq_view_get(self._ctx, q, C.byref(v)))
+        return v
+
+    def waitq_append_device(self, q, d_tok, d_mflags, n: int, d_order, d_offsets, d_disp, stream=None) -> None:
+        """After admit_device on the same stream: every ADM_ENQUEUE message joins its activation's FIFO in arrival order
+        (ActivationData.EnqueueMessage, ActivationData.cs:487-514), and an activation without Running records the token
+        of its bucket's first ADM_RUN message (RecordRunning, :411-422).  d_tok: one uint32 token per message.  Raises
+        E_CAPACITY, with nothing changed, when the store could pass the queue's capacity."""
+        self._ck(self._lib.orl_waitq_append_device(self._ctx, q, ptr(d_tok), ptr(d_mflags), int(n), ptr(d_order),
+                                                   ptr(d_offsets), ptr(d_disp), ptr(stream)))
+
+    def complete_device(self, q, d_cact, d_ctok, m: int, d_corder, d_coffsets, d_state, d_counts=None, stream=None) -> None:
+        """Request completion and the message pump for m records (activation, token), bucketed by bucket_device on the
+        same stream: ResetRunning (ActivationData.cs:424-442), InFlightCount-- (InvokeWorkItem.cs:70,79) and
+        Dispatcher.RunMessagePump (Dispatcher.cs:633-685) per activation, Running's own completion first.  TOK_NONE asks
+        for a pump only (Catalog.cs:1093), TOK_DRAIN for DequeueAllWaitingMessages (ActivationData.cs:590-599).  The
+        messages to run next (WQ_RUN) and the drained ones are the queue's out list (waitq_view); d_state is updated in
+        place.  d_counts: 8 uint64 (written; the CMP_* order)."""
+        self._ck(self._lib.orl_complete_device(self._ctx, q, ptr(d_cact), ptr(d_ctok), int(m), ptr(d_corder),
+                                               ptr(d_coffsets), ptr(d_state), ptr(d_counts), ptr(stream)))
 
     def copy_to_host(self, h_dst: np.ndarray, d_src, nbytes: Optional[int] = None, stream=None) -> np.ndarray:
         """orl_copy_to_host + orl_stream_sync (the P/Invoke caller's way to read device outputs)."""
