@@ -341,6 +341,23 @@ int orl_route_batch_device(orl_ctx* ctx, const orl_msg_hdr* d_in, size_t n, uint
  * routed as in orl_route_batch_device; pub_offsets[n_pub+1] (device) maps publishes to output ranges.
  * *n_out (host) receives the number of emitted messages (this call synchronises `stream` once to read it,
  * unless opts has ORL_OPT_TOTAL_GIVEN and *n_out already holds that count).
+ * Preconditions of every stage-5 entry point (orl_fanout_*_device, orl_node_fanout_batch_device):
+ *   - a publisher may have no follower (csr_off[pubs[p]] == csr_off[pubs[p]+1]): it emits nothing and its
+ *     pub_offsets entry repeats the next publisher's; leading, trailing and whole runs of them are fine, and so is a
+ *     batch that emits nothing (n_pub == 0 included: pubs and pub_silo may then be NULL);
+ *   - d_csr_tgt must hold at least one element even when nothing is emitted (the 32-B-table kernel's idle lanes
+ *     prefetch csr_tgt[0]);
+ *   - every out-degree and the emitted total (n_direct excluded) must be below 2^32: the degree scan is 32-bit and a
+ *     larger sum wraps without an error.
+ * ORL_OPT_TOTAL_GIVEN with *n_out = n:
+ *   - n above the real total (overstated): outputs [real, n) are ORL_ST_PAST_TOTAL / ORL_NO_ACT, in the unresolved
+ *     bucket (orl_fanout_expand_device: null headers, below);
+ *   - n below it (understated, but >= n_direct): the call handles the first n messages of the batch only: route, act
+ *     (records for orl_fanout_expand_device) [0, n) are those of the whole batch, order and bucket_offsets are the
+ *     stage 4 of these n alone, nothing is written at or past n, and *n_out stays n.  pub_offsets is still the whole
+ *     expansion's (its last entries exceed n).  No error is raised: the device never reports the real total here.
+ *   - n below n_direct (orl_fanout_route_mixed_device): ORL_E_INVALID, checked on the host before anything is
+ *     enqueued; no output is written.
  * Reference: ChirperAccount.PublishMessage fan-out loop (Samples/Chirper/ChirperGrains/ChirperAccount.cs:154-157),
  * ObserverSubscriptionManager.Notify (src/Orleans/Async/ObserverSubscriptionManager.cs:111-139). */
 int orl_fanout_route_device(orl_ctx* ctx, const uint64_t* d_csr_off, const uint32_t* d_csr_tgt,
