@@ -797,7 +797,7 @@ void free_device(orl_ctx* c) {
         if (L.ev) (void)hipEventDestroy(L.ev);
         L = Scratch::LbSet{};
     }
-    f(c->s.sw_ring); f(c->s.sw_ctl); f(c->s.sw_gtot); f(c->s.sw_gmax); f(c->s.s4_err);
+    f(c->s.s4_err);
     if (c->s.hot_host) (void)hipHostFree(c->s.hot_host);
     f(c->st_in); f(c->st_out); f(c->st_off);
     for (auto& e : c->tev) if (e) (void)hipEventDestroy(e);
@@ -930,26 +930,6 @@ int orl_ctx_create(const orl_config* cfg, orl_ctx** out) {
             if ((e = hipMalloc((void**)&c->s.lsd_hot, 16)) != hipSuccess) return bail(e, "hipMalloc(lsd_hot)");
         if ((e = hipMalloc((void**)&c->s.s4_err, 4)) != hipSuccess) return bail(e, "hipMalloc(s4_err)");
         if ((e = hipMemset(c->s.s4_err, 0, 4)) != hipSuccess) return bail(e, "hipMemset(s4_err)");
-        // the LSD plan's single-sweep passes (opt-in, ORL_LSD_SWEEP=1 at context creation: measured 8x slower than the
-        // k_hist_pairs passes on MI355X): a look-back ring of >= `tiles` rows, zeroed once
-        const char* sweep_env = getenv("ORL_LSD_SWEEP");
-        if (!bp.two_level && sweep_env && sweep_env[0] == '1') {
-            uint32_t row_bits = 0, rbits = 0;
-            for (int p = 0; p < bp.lsd.passes; ++p) row_bits = std::max<uint32_t>(row_bits, (uint32_t)bp.lsd.bits[p]);
-            while ((1ull << rbits) < tiles) ++rbits;
-            const uint64_t ring_bytes = (8ull << rbits) << row_bits;
-            if (ring_bytes <= (4ull << 30) && bp.lsd.passes <= 3) {  // else the k_hist_pairs passes (no ring)
-                if ((e = hipMalloc((void**)&c->s.sw_ring, ring_bytes)) != hipSuccess) return bail(e, "hipMalloc(sweep ring)");
-                if ((e = hipMemset(c->s.sw_ring, 0, ring_bytes)) != hipSuccess) return bail(e, "hipMemset(sweep ring)");
-                if ((e = hipMalloc((void**)&c->s.sw_ctl, 16)) != hipSuccess) return bail(e, "hipMalloc(sweep ctl)");
-                if ((e = hipMemset(c->s.sw_ctl, 0, 16)) != hipSuccess) return bail(e, "hipMemset(sweep ctl)");
-                if ((e = hipMalloc((void**)&c->s.sw_gtot, (3ull << kMaxDigitBits) * 4)) != hipSuccess) return bail(e, "hipMalloc(sweep totals)");
-                if ((e = hipMemset(c->s.sw_gtot, 0, (3ull << kMaxDigitBits) * 4)) != hipSuccess) return bail(e, "hipMemset(sweep totals)");
-                if ((e = hipMalloc((void**)&c->s.sw_gmax, (1ull << kMaxDigitBits) * 4)) != hipSuccess) return bail(e, "hipMalloc(sweep max)");
-                c->s.sw_rbits = rbits;
-                c->s.sw_row_bits = row_bits;
-            }
-        }
         if ((e = hipMalloc((void**)&c->s.gap_q, kGapQueueWords * 4)) != hipSuccess) return bail(e, "hipMalloc(gap_q)");
         if ((e = hipMemset(c->s.gap_q, 0, kGapQueueWords * 4)) != hipSuccess) return bail(e, "hipMemset(gap_q)");
         if ((e = hipMalloc((void**)&c->s.digits, mb)) != hipSuccess) return bail(e, "hipMalloc(digits)");

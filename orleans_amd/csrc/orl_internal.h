@@ -339,8 +339,8 @@ struct Scratch {
     uint32_t* col_tot;      // [2048 + 1] column totals (+ the hot key's at [bins])
     uint8_t* digits;        // [max_batch] (partition by owner)
     uint32_t* seg_hist;     // [max segments][2^lb] two-level path: per-segment low-digit counts → bases
-    uint32_t* seg_carry;    // [seg_lb_cap][2^lb] skewed plans: each segment chunk's carry-in (legacy scan: chunk sums first)
-    uint32_t* seg_meta;     // [seg_lb_cap] skewed plans: each chunk's first bucket (+ shape bits in the legacy scan)
+    uint32_t* seg_carry;    // [seg_lb_cap][2^lb] skewed plans: each segment chunk's carry-in (k_seg_scan: chunk sums first)
+    uint32_t* seg_meta;     // [seg_lb_cap] skewed plans: each chunk's first bucket (+ shape bits from k_seg_scan)
     uint32_t* seg_lb = nullptr;     // [2][seg_lb_cap][2^lb] fused level 2, skewed plans: chunk aggregate rows, inclusive rows
     uint32_t* seg_lbctl = nullptr;  // [4 + seg_lb_cap] ticket, done count, -, -, then one look-back flag per chunk (zeroed once)
     uint32_t seg_lb_cap = 0;        // chunks of kSegLbMinRows segments the look-back buffers hold
@@ -380,16 +380,7 @@ struct Scratch {
     uint32_t fan_blk_cap = 0;
     uint32_t gap_cap = 4096;  // LSD offsets' long-gap queue capacity (env_gap_cap() at context creation)
     int fan_u = 1;            // fan-out messages per thread and step (env_fan_u() at context creation)
-    // LSD plan in single-sweep passes (round 6, k_sweep): look-back ring [1 << sw_rbits][1 << sw_row_bits] u64 (zeroed once),
-    // control words {next ticket, launch base, done, -} (zeroed once), digit totals [3][2^kMaxDigitBits], each final digit's
-    // largest key's low bits [2^kMaxDigitBits].  sw_ring == nullptr: the context's plan is two-level, or the ring would not
-    // fit its budget — the LSD plan then takes the k_hist_pairs passes.
-    unsigned long long* sw_ring = nullptr;
-    uint32_t sw_rbits = 0, sw_row_bits = 0;
-    uint32_t* sw_ctl = nullptr;
-    uint32_t* sw_gtot = nullptr;
-    uint32_t* sw_gmax = nullptr;
-    // stage 4's look-back error word (the fused level-2 kernel's skewed form, k_sweep): |= 1 when a look-back gave up (a
+    // stage 4's look-back error word (the fused level-2 kernel's skewed form): |= 1 when a look-back gave up (a
     // device fault); read and cleared by ORL_Q_STAGE4_ERROR, checked by the node after every host-side stage 4.
     uint32_t* s4_err = nullptr;
 };

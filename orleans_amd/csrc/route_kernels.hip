@@ -409,31 +409,6 @@ __device__ __forceinline__ uint32_t dest_rank_cached(const RouteParams& P, const
     return owner == 0xFFu ? my_rank : rank_of_silo[owner];
 }
 
-// route_msg over the compact probe table for local owners (remote owners with the cache on: route_msg).
-// (the fan-out kernel reads the 16-B form; see launch_fanout_route_bucket)
-__device__ __forceinline__ uint32_t route_msg16(const RouteParams& P, const DirSlot* __restrict__ dir, uint64_t dmask,
-                                                const ProbeSlot* __restrict__ probe, const DirSlot* __restrict__ cache,
-                                                uint64_t cmask, const Msg& m, bool excl_opt, uint32_t& act) {
-    uint32_t h, owner, rf;
-    act = ORL_NO_ACT;
-    const uint32_t r = route_head(P, m, excl_opt, h, owner, rf);
-    if (r < kNeedProbeCache) return r;
-    if (r == kNeedProbeCache) return route_msg(P, dir, dmask, cache, cmask, m, excl_opt, act, 0u);
-    uint32_t fact = 0, fsilo = 0;
-    int st = 1;
-    const uint32_t mk = probe_type(P, m);
-    if (mk != kNoType) {
-        const u32x4* p4 = reinterpret_cast<const u32x4*>(probe);
-        uint64_t slot = dir_slot(h, dmask);
-        st = probe_slot16(p4[slot], m.n1, mk, fact, fsilo);
-        for (uint64_t step = 0; st == 2 && step < dmask; ++step) {
-            slot = (slot + 1) & dmask;
-            st = probe_slot16(p4[slot], m.n1, mk, fact, fsilo);
-        }
-    }
-    return route_tail(P, m, h, owner, rf, st == 0, fact, fsilo, act, false);
-}
-
 __device__ __forceinline__ uint32_t bucket_key(uint32_t act, uint32_t n_act) { return act < n_act ? act : n_act; }
 
 // A tile's digit counts as one u16 row of the count matrix (a tile holds <= 4096 elements, so every count fits): two
@@ -1167,22 +1142,6 @@ __global__ __launch_bounds__(256) void k_scan_sums(uint32_t* __restrict__ sums, 
     }
 }
 
-// 16 consecutive u32 of a thread (4 x 16-B loads when they are all in range and the caller's array is 16-B aligned;
-// `fill` past m).
-__device__ __forceinline__ void load16(const uint32_t* __restrict__ a, uint64_t base, uint64_t m, uint32_t fill, uint32_t (&v)[16]) {
-    if (base + 16 <= m && (reinterpret_cast<uintptr_t>(a) & 15u) == 0) {
-        const uint4* p = reinterpret_cast<const uint4*>(a + base);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint4 x = p[q];
-            v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = base + i < m ? a[base + i] : fill;
-    }
-}
-
 template <int E>
 __device__ __forceinline__ void load_e(const uint32_t* __restrict__ a, uint64_t base, uint64_t m, uint32_t fill, uint32_t (&v)[E]) {
     static_assert(E % 4 == 0, "whole 16-B vectors");
@@ -1208,18 +1167,6 @@ __device__ __forceinline__ void store_e(uint32_t* __restrict__ a, uint64_t base,
     } else {
 #pragma unroll
         for (int i = 0; i < E; ++i)
-            if (base + i < m) a[base + i] = v[i];
-    }
-}
-
-__device__ __forceinline__ void store16(uint32_t* __restrict__ a, uint64_t base, uint64_t m, const uint32_t (&v)[16]) {
-    if (base + 16 <= m && (reinterpret_cast<uintptr_t>(a) & 15u) == 0) {
-        uint4* p = reinterpret_cast<uint4*>(a + base);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) p[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
             if (base + i < m) a[base + i] = v[i];
     }
 }
@@ -1340,9 +1287,7 @@ __device__ __forceinline__ uint4 ld_s4(const uint4* p) {
     return *p;
 }
 
-// DIG8: the input is the previous LSD pass's digit stream (OUT_PAIR_DIG: this pass's digit of every pair, one byte each, in
-// the pairs' order) instead of the pairs: 1 B read per element instead of 8 (round 6).
-template <bool ACTS, bool DIG8 = false>
+template <bool ACTS>
 __global__ __launch_bounds__(256) void k_hist_pairs(const void* __restrict__ in, uint32_t n, uint32_t n_act, uint32_t shift,
                                                     uint32_t bins, uint16_t* __restrict__ tile_cnt,
                                                     const uint32_t* __restrict__ hot_words = nullptr,
@@ -1372,37 +1317,6 @@ __global__ __launch_bounds__(256) void k_hist_pairs(const void* __restrict__ in,
                 else atomicAdd(&hist[(k[j] >> shift) & (bins - 1)], 1u);
             }
         if (hot_rows) wave_add_hot(&hot, hot_mine);
-    } else if (DIG8) {
-        // 16 consecutive elements per thread (one 16-B load): sorted by the previous digit, so equal digits come in runs,
-        // each added with one atomic (a hot key's run as well)
-        const uint8_t* dg = static_cast<const uint8_t*>(in);
-        const uint32_t e0 = base + threadIdx.x * 16u;
-        if (e0 < n) {
-            uint32_t v[4];
-            if (e0 + 16u <= n) {
-                const uint4 q = ld_s4(reinterpret_cast<const uint4*>(dg + e0));
-                v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-            } else {
-                for (uint32_t i = 0; i < 4; ++i) v[i] = 0;
-                for (uint32_t i = 0; e0 + i < n; ++i) v[i >> 2] |= (uint32_t)dg[e0 + i] << (8u * (i & 3u));
-            }
-            const uint32_t m = min(16u, n - e0);
-            uint32_t cur = v[0] & 0xFFu, len = 1;
-#pragma unroll
-            for (uint32_t i = 1; i < 16; ++i) {
-                if (i < m) {
-                    const uint32_t b = (v[i >> 2] >> (8u * (i & 3u))) & 0xFFu;
-                    if (b == cur) {
-                        ++len;
-                    } else {
-                        atomicAdd(&hist[cur], len);
-                        cur = b;
-                        len = 1;
-                    }
-                }
-            }
-            atomicAdd(&hist[cur], len);
-        }
     } else {
         // pairs of an LSD pass: sorted by the previous digit, so a hot key's pairs sit in consecutive lanes.  Loads stay
         // coalesced (element j * 256 + x); each run of equal digits inside a 64-lane step adds its length with one
@@ -1432,10 +1346,11 @@ __global__ __launch_bounds__(256) void k_hist_pairs(const void* __restrict__ in,
     if (ACTS && hot_rows && threadIdx.x == 0) hot_rows[blockIdx.x] = hot;
 }
 
-// The digit stream's histogram with one WAVE per 4096-element tile (round 6; k_hist_pairs<false, true> is the form with one
-// workgroup per tile): a lane loads 64 consecutive digits (4 x 16 B, all in flight), adds each run of equal digits with one
-// atomic to its wave's private 256-bin row in LDS, and the wave stores its tile's row — no workgroup barrier, a quarter of
-// the workgroups (the per-tile form spent its time in launch, zeroing and barriers: 0.15 ms per 256M for 256 MB read).
+// The histogram of an LSD pass's digit stream (OUT_PAIR_DIG: this pass's digit of every pair, one byte each, in the pairs'
+// order: 1 B read per element instead of 8) with one WAVE per 4096-element tile (round 6): a lane loads 64 consecutive
+// digits (4 x 16 B, all in flight), adds each run of equal digits with one atomic to its wave's private 256-bin row in LDS,
+// and the wave stores its tile's row — no workgroup barrier, a quarter of the workgroups (a form with one workgroup per
+// tile spent its time in launch, zeroing and barriers: 0.15 ms per 256M for 256 MB read, profiles/r06x_dig8_wave_ab.txt).
 // n_dev as k_hist_pairs.  bins <= 256.
 // Q: 16-B loads per lane (the tile is 64 x 16 x Q digits: 4096 for Q = 4, 3072 for the 12-item passes).
 // TW: tiles per wave (2 measured no faster: 133 vs 131 us per pass at config 3, profiles/r06tw_config3_kernel_stats.txt —
@@ -1603,7 +1518,7 @@ __device__ void seg_plan_body(const uint32_t* __restrict__ col_tot, uint32_t nbk
 // plan_bstart (the two-level stage 4 with an MSD pass): one more grid column does k_seg_plan's work over the column
 // totals T — the segment plan is ready before the MSD pass, one launch fewer (round 4).
 // A small fan-out batch (at most kSelfScanChunks chunks of 64 rows, no hot column) has its chunk sums S accumulated by the
-// fan-out kernel's atomics instead of k_col_sum (ORL_COL_SELF=0: k_col_sum; measured -1 us at config 5).
+// fan-out kernel's atomics instead of k_col_sum (measured -1 us at config 5).
 constexpr uint32_t kSelfScanChunks = 64;
 constexpr uint32_t kApplyCols = 64;                        // columns per k_col_apply block, one per lane
 constexpr uint32_t kApplyGroups = 256 / kApplyCols;        // row groups per chunk, one per wave
@@ -1685,15 +1600,12 @@ __device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t nb) {
 //   3. per-bin tile-local starts (block scan) and delta[d] = global base of (tile, d) - local start;
 //   4. scatter into an LDS image sorted by digit, then write it out in image order, so the global stores
 //      are runs of consecutive positions per bin.  OUT_PAIR writes 8-B {key, index} pairs (one store
-//      request per run instead of two); OUT_FINAL writes the index to `order` and the key to `keys`;
-//      OUT_SOA8 / OUT_SOA16 (the MSD pass of the two-level path) write the index to `order` (an index array) and only
-//      the key's low `shift` bits — the level-2 digit, all that level 2 reads of the key — as u8 / u16 to `keys`.
+//      request per run instead of two); OUT_FINAL writes the index to `order` and the key to `keys`.
 // Tiles are taken in XCD-aware order (xcd_tile) so consecutive tiles' runs of one bin meet in one L2.
-enum : int { IN_ACT = 0, IN_PAIR = 1, IN_SOA8 = 2, IN_SOA16 = 3 };
-enum : int { OUT_PAIR = 0, OUT_FINAL = 1, OUT_SOA8 = 2, OUT_SOA16 = 3, OUT_LSD_PAIR = 4, OUT_PAIR_SMALL = 5, OUT_FINAL_GAPS = 6,
-              OUT_PAIR_DIG = 7 };
+enum : int { IN_ACT = 0, IN_PAIR = 1 };
+enum : int { OUT_PAIR = 0, OUT_FINAL = 1, OUT_LSD_PAIR = 4, OUT_PAIR_SMALL = 5, OUT_FINAL_GAPS = 6, OUT_PAIR_DIG = 7 };
 // PAIR_DIG (an LSD pass followed by one of <= 8 bits, round 6): the pairs, plus the next pass's digit of each as one byte to
-// key_out (dsel = next shift | next bits << 8), so that pass's histogram (k_hist_pairs<false, true>) reads 1 B per element.
+// key_out (dsel = next shift | next bits << 8), so that pass's histogram (k_hist_dig8_wave) reads 1 B per element.
 // FINAL_GAPS (the LSD plan's last pass, round 6): `order` plus the bucket offsets instead of the sorted keys — see
 // k_bound_last.
 // LSD_PAIR: an LSD pass's pairs; PAIR_SMALL: the MSD pass's pairs from 2048-element tiles (kMsdItemsSmall, small batches)
@@ -1795,7 +1707,7 @@ constexpr uint32_t kFlEmpty = 0x0000FFFFu;
 constexpr uint32_t kGapWave = 16, kGapChunk = 32768, kGapCap = 4096, kGapLds = 4096, kGapPer = 8, kGapBlock = 256 * kGapPer;
 
 // Bucket offsets [lo, lo + len) = val, straight to HBM: a short gap by its lane, a long one by the whole wave (64 entries
-// per store), pieces of kGapChunk queued for k_sweep_tail while the queue has room.  Every lane of the wave calls it.
+// per store), pieces of kGapChunk queued for k_offsets_tail while the queue has room.  Every lane of the wave calls it.
 __device__ __forceinline__ void write_gap(uint32_t* __restrict__ offsets, uint32_t lo, uint32_t len, uint32_t val,
                                           uint32_t* __restrict__ q, uint32_t cap) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -1981,136 +1893,12 @@ __global__ __launch_bounds__(256) void k_radix_pass(const void* __restrict__ in,
             } else if (OUT == OUT_PAIR_DIG) {
                 pair_out[g] = kv;
                 reinterpret_cast<uint8_t*>(key_out)[g] = (uint8_t)((k >> (dsel & 31u)) & ((1u << (dsel >> 8)) - 1u));
-            } else if (OUT == OUT_SOA8) {
-                order_out[g] = kv.y;
-                reinterpret_cast<uint8_t*>(key_out)[g] = (uint8_t)(k & ((1u << shift) - 1u));
-            } else if (OUT == OUT_SOA16) {
-                order_out[g] = kv.y;
-                reinterpret_cast<uint16_t*>(key_out)[g] = (uint16_t)(k & ((1u << shift) - 1u));
             } else {
                 key_out[g] = k;
                 order_out[g] = kv.y;
             }
         }
     }
-}
-
-// Round-2 bucket offsets (ORL_OFFSETS_SUFMIN=1, A/B against k_offsets_gaps below), over an offsets array pre-filled
-// with kNoOffset:
-//   k_offsets_mark: one streaming read of the sorted keys; every position i whose key differs from key[i-1]
-//                   starts bucket key[i] (16 keys per thread, 4 x 16-B loads);
-//   the empty buckets (still kNoOffset) then get the next present key's start by suffix minima (k_sufmin_*).
-constexpr uint32_t kNoOffset = 0xFFFFFFFFu;
-
-__global__ __launch_bounds__(256) void k_fill_u32(uint32_t* __restrict__ a, uint32_t m, uint32_t v) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < m) a[i] = v;
-}
-
-__global__ __launch_bounds__(256) void k_offsets_mark(const uint32_t* __restrict__ sorted, uint32_t n, uint32_t nb,
-                                                      uint32_t* __restrict__ offsets) {
-    const uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u;
-    if (i0 >= n) return;
-    uint32_t k[16];
-    if (i0 + 16 <= n) {
-        const uint4* p = reinterpret_cast<const uint4*>(sorted + i0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint4 v = p[q];
-            k[4 * q] = v.x; k[4 * q + 1] = v.y; k[4 * q + 2] = v.z; k[4 * q + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) k[q] = (i0 + q < n) ? sorted[i0 + q] : k[q > 0 ? q - 1 : 0];
-    }
-    uint32_t prev = i0 ? sorted[i0 - 1] : kNoOffset;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        if (i0 + q < n && k[q] != prev && k[q] < nb) offsets[k[q]] = (uint32_t)(i0 + q);
-        prev = k[q];
-    }
-}
-
-// Empty buckets by a suffix-min scan instead of one binary search per key (306 us at config 3, whose
-// 16M handles are mostly absent from a Zipf batch): present keys hold their first position and positions grow with
-// the key, so offsets[b] = min(offsets[b .. nb), n) is lower_bound(sorted, b) for every b.  In 4096-element chunks:
-// chunk minima; their exclusive suffix minima (one block); each chunk rescanned from its end.
-__device__ __forceinline__ uint32_t wave_incl_suffix_min(uint32_t v) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_down(v, d, 64);
-        if (lane + d < 64) v = min(v, t);
-    }
-    return v;
-}
-
-// Minimum over the threads after this one (256 threads; `after_all` = the value past the last thread).
-__device__ __forceinline__ uint32_t block_excl_suffix_min(uint32_t v, uint32_t* wmin, uint32_t after_all) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_suffix_min(v);
-    if (lane == 0) wmin[w] = incl;
-    __syncthreads();
-    uint32_t later = after_all;  // waves after w
-    for (uint32_t i = w + 1; i < kWaves; ++i) later = min(later, wmin[i]);
-    const uint32_t next = __shfl_down(incl, 1, 64);
-    __syncthreads();
-    return lane == 63 ? later : min(next, later);
-}
-
-__global__ __launch_bounds__(256) void k_sufmin_reduce(const uint32_t* __restrict__ a, uint32_t m, uint32_t* __restrict__ mins) {
-    __shared__ uint32_t wmin[kWaves];
-    const uint32_t base = blockIdx.x * kScanChunk;
-    uint32_t v = 0xFFFFFFFFu;
-#pragma unroll
-    for (uint32_t i = 0; i < kScanChunk / 256; ++i) {
-        const uint32_t e = base + i * 256 + threadIdx.x;
-        if (e < m) v = min(v, a[e]);
-    }
-    const uint32_t inc = wave_incl_suffix_min(v);
-    if ((threadIdx.x & 63u) == 0) wmin[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t r = wmin[0];
-        for (uint32_t i = 1; i < kWaves; ++i) r = min(r, wmin[i]);
-        mins[blockIdx.x] = r;
-    }
-}
-
-// One block: mins[c] becomes min(mins[c + 1 ..], tail), walking the chunks from the end 256 at a time.
-__global__ __launch_bounds__(256) void k_sufmin_chunks(uint32_t* __restrict__ mins, uint32_t nch, uint32_t tail) {
-    __shared__ uint32_t wmin[kWaves];
-    uint32_t carry = tail;
-    for (int64_t hi = (int64_t)nch; hi > 0; hi -= 256) {
-        const int64_t i = hi - 256 + threadIdx.x;  // this round covers [hi - 256, hi)
-        const uint32_t v = i >= 0 ? mins[i] : 0xFFFFFFFFu;
-        const uint32_t ex = block_excl_suffix_min(v, wmin, carry);
-        const uint32_t all = min(v, ex);  // thread 0's inclusive value = the round's minimum with the carry
-        if (i >= 0) mins[i] = ex;
-        __shared__ uint32_t s_all;
-        if (threadIdx.x == 0) s_all = all;
-        __syncthreads();
-        carry = s_all;
-        __syncthreads();
-    }
-}
-
-// Each thread owns 16 consecutive elements of the chunk.
-__global__ __launch_bounds__(256) void k_sufmin_down(uint32_t* __restrict__ a, uint32_t m, const uint32_t* __restrict__ mins) {
-    __shared__ uint32_t wmin[kWaves];
-    const uint32_t base = blockIdx.x * kScanChunk + threadIdx.x * 16u;
-    uint32_t v[16];
-    load16(a, base, m, 0xFFFFFFFFu, v);
-    uint32_t tmin = 0xFFFFFFFFu;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) tmin = min(tmin, v[i]);
-    uint32_t run = block_excl_suffix_min(tmin, wmin, mins[blockIdx.x]);
-#pragma unroll
-    for (int i = 15; i >= 0; --i) {
-        run = min(run, v[i]);
-        v[i] = run;
-    }
-    store16(a, base, m, v);
 }
 
 // Bucket offsets from the sorted keys in one pass, every entry written exactly once (replaces fill + mark + the three
@@ -2215,301 +2003,25 @@ __global__ __launch_bounds__(256) void k_offsets_long(uint32_t* __restrict__ off
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Stage 4, LSD plan (keys of > 2 x kMaxDigitBits bits: config 3's 24-bit handles, config 4's 10M accounts) in
-// single-sweep passes (round 6).  Rounds 2-5 gave every pass after the first a histogram pass
-// (k_hist_pairs: a re-read of the pairs the previous pass had just written) and a column scan of per-tile count rows,
-// and the last pass wrote the sorted keys for k_offsets_gaps to read back.  Here:
-//   k_digit_hist  one read of the handles counts the digits of every pass at once (global totals, no per-tile rows);
-//   k_sweep       each pass ranks its tile in LDS as k_radix_pass does and takes each digit's output base from the
-//                 digit's global start + a decoupled look-back over the earlier tiles' published per-digit counts (tiles
-//                 numbered by a ticket taken at start, so every tile a look-back waits on has started);
-//   FINAL         the last pass writes `order` and the bucket offsets, nothing else: its tile image is sorted by the
-//                 whole key (its input is sorted by the lower digits and the pass is stable), so the first message of
-//                 every key knows its predecessor key — the image's previous element, or, for a digit's first message
-//                 in the tile, the largest key of that digit in the earlier tiles, which the look-back carries beside
-//                 the count — and writes offsets[] for every bucket in between; k_sweep_tail writes the buckets past
-//                 each digit's largest key.  Every offset is written once.
-// Look-back state: a ring of rows [R][2^row_bits] of u64 words indexed by ticket (R a power of two >= the context's tiles,
-// so a launch never reuses a row and a row's older word belongs to a finished launch; one row width per context, so the
-// passes of one plan index the ring alike):
-//   bits 0-31 count, 32-53 the low `shift` bits of the largest key (FINAL), 54-55 kind (1 aggregate: this tile's count;
-//   2 inclusive: this and every earlier tile; 0 unpublished), 56-63 tag = (ticket >> log2 R) & 0xFF (a word the ring's
-//   previous round wrote reads as unpublished).
-// ctl = {next ticket, first ticket of this launch, workgroups done}: the last workgroup out moves the launch base on, so
-// nothing is reset by the host between launches and a captured hipGraph replays correctly.  A look-back that gives up
-// (a device fault: every awaited tile has started) sets the context's stage-4 error word (ORL_Q_STAGE4_ERROR).
-constexpr uint32_t kSweepSpin = 1u << 22;
-constexpr uint32_t kSweepWin = 4;  // earlier tiles whose words one look-back round trip loads per digit
-constexpr uint32_t kSweepMkMask = 0x3FFFFFu;
+// The LSD plan's bucket offsets without the sorted keys (round 6, VERDICT r5 item 3).  Its last pass (k_radix_pass
+// OUT_FINAL_GAPS) has each tile's image sorted by the whole key (the input is sorted by the lower digits, the pass is
+// stable), so it writes the buckets between consecutive keys of one digit inside the tile itself, and one row per tile of
+// FL[t][d] = each digit's first and last key's low 16 bits (the plan's last shift is <= 16 for this form).  What crosses
+// tiles — the buckets between the last key of digit d in the nearest earlier tile that has one and the first key of d in
+// tile t — is three column launches over the [tiles][2^bits] rows the pass already has (its counts C, its output bases M):
+//   k_bound_last   S[c][d] = the last key of d in chunk c of kScanRows tiles (kFlNone: no message of d there);
+//   k_bound_scan   P[c][d] = the last key of d in the chunks before c; gmax[d] = the last key of d overall;
+//   k_bound_apply  every tile with messages of d: offsets[(d << shift) + prev + 1, (d << shift) + first] = M[t][d];
+// then k_offsets_tail: the buckets past each digit's last key.  2 GB less traffic per 256M messages than writing the sorted
+// keys and reading them back (k_offsets_gaps), and every offset is still written exactly once.
 
-template <int BITS>
-struct SweepSmem {
-    uint32_t cnt[kWaves][(1u << BITS) / 2u];  // packed per-wave counts -> per-wave starts; then the bins' deltas
-    uint2 stage[kTile];                       // the tile image, sorted by digit
-    uint32_t prev[1u << BITS];                // FINAL: the key before each digit's first message of the tile
-    uint32_t wsum[kWaves];
-    uint32_t tile, tick;
-};
-
-__device__ __forceinline__ unsigned long long sweep_word(uint32_t tag, uint32_t kind, uint32_t mk, uint32_t count) {
-    return ((unsigned long long)tag << 56) | ((unsigned long long)kind << 54) | ((unsigned long long)(mk & kSweepMkMask) << 32) |
-           count;
-}
-
-// One read of the handles: gtot[p << kMaxDigitBits | d] += messages whose pass-p digit is d (gtot zero: at context creation,
-// then by the previous batch's k_sweep_tail).
-// 16 handles per thread and step (four 16-B loads in flight); per-workgroup LDS counts, flushed with one atomic per bin.
-__global__ __launch_bounds__(256) void k_digit_hist(const uint32_t* __restrict__ act, uint32_t n, uint32_t n_act,
-                                                    uint32_t passes, uint32_t sh0, uint32_t sh1, uint32_t sh2, uint32_t m0,
-                                                    uint32_t m1, uint32_t m2, uint32_t* __restrict__ gtot) {
-    __shared__ uint32_t h[3][1u << kMaxDigitBits];
-    for (uint32_t b = threadIdx.x; b < 3u << kMaxDigitBits; b += 256) (&h[0][0])[b] = 0;
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * 256u * 16u;
-    for (uint64_t i0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 16u; i0 < n; i0 += stride) {
-        uint32_t k[16];
-        if (i0 + 16 <= n) {
-            const uint4* p = reinterpret_cast<const uint4*>(act + i0);
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint4 v = ld_s4(p + j);
-                k[4 * j] = v.x; k[4 * j + 1] = v.y; k[4 * j + 2] = v.z; k[4 * j + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (uint32_t j = 0; j < 16; ++j) k[j] = i0 + j < n ? act[i0 + j] : 0u;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 16; ++j) {
-            if (i0 + j >= n) break;
-            const uint32_t kk = bucket_key(k[j], n_act);
-            atomicAdd(&h[0][(kk >> sh0) & m0], 1u);
-            if (passes > 1) atomicAdd(&h[1][(kk >> sh1) & m1], 1u);
-            if (passes > 2) atomicAdd(&h[2][(kk >> sh2) & m2], 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < 3u << kMaxDigitBits; b += 256) {
-        const uint32_t v = (&h[0][0])[b];
-        if (v) atomicAdd(gtot + b, v);
-    }
-}
-
-// One single-sweep LSD pass over a 4096-element tile (see above).  IN: IN_ACT (handles, clamped to n_act; index =
-// position) or IN_PAIR ({key, index} of the previous pass).  Not FINAL: {key, index} pairs to pair_out.  FINAL: indices to
-// order_out, the bucket offsets to offsets[0, nb) (k_sweep_tail completes them), each digit's largest key's low bits to
-// gmax (by the last tile).  gtot: this pass's global digit totals.
-template <int BITS, int IN, bool FINAL, int RM>
-__global__ __launch_bounds__(256) void k_sweep(const void* __restrict__ in, uint32_t n, uint32_t n_act, uint32_t shift,
-                                               const uint32_t* __restrict__ gtot, unsigned long long* __restrict__ ring,
-                                               uint32_t rbits, uint32_t row_bits, uint32_t* __restrict__ ctl, uint32_t ntiles,
-                                               uint2* __restrict__ pair_out, uint32_t* __restrict__ order_out,
-                                               uint32_t* __restrict__ offsets, uint32_t nb, uint32_t* __restrict__ gmax,
-                                               uint32_t* __restrict__ gap_q, uint32_t gap_cap, uint32_t* __restrict__ err_word) {
-    constexpr uint32_t B = 1u << BITS, PER = kDigitsPerThread<BITS>;
-    __shared__ SweepSmem<BITS> sm;
-    const uint32_t rflags = rank_flags();
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    for (uint32_t b = threadIdx.x; b < B / 2u; b += 256) {
-#pragma unroll
-        for (uint32_t q = 0; q < kWaves; ++q) sm.cnt[q][b] = 0;
-    }
-    if (threadIdx.x == 0) {
-        const uint32_t tk = atomicAdd(&ctl[0], 1u);
-        sm.tick = tk;
-        sm.tile = tk - __hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const uint32_t tile = sm.tile, tick = sm.tick;
-    const uint32_t rmask = (1u << rbits) - 1u;
-    const uint32_t tbase = tile * kTile, wbase = tbase + w * (kItems * 64u);
-    uint32_t key[kItems], idx[kItems], rank[kItems];
-#pragma unroll
-    for (uint32_t j = 0; j < kItems; ++j) {  // unconditional (clamped) loads: all in flight together
-        const uint32_t e = wbase + j * 64u + lane;
-        const uint32_t ec = e < n ? e : n - 1;
-        if (IN == IN_ACT) {
-            key[j] = bucket_key(ld_s4(static_cast<const uint32_t*>(in) + ec), n_act);
-            idx[j] = e;
-        } else {
-            const uint2 v = ld_s4(static_cast<const uint2*>(in) + ec);
-            key[j] = v.x;
-            idx[j] = v.y;
-        }
-    }
-    // each digit's global start: the exclusive prefix of the pass's digit totals (thread t owns digits [t*PER, t*PER+PER))
-    uint32_t gs[PER];
-    {
-        uint32_t acc = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < PER; ++q) {
-            const uint32_t d = threadIdx.x * PER + q;
-            gs[q] = d < B ? gtot[d] : 0u;
-            acc += gs[q];
-        }
-        uint32_t total;
-        uint32_t run = block_excl_scan(acc, sm.wsum, total);
-#pragma unroll
-        for (uint32_t q = 0; q < PER; ++q) {
-            const uint32_t v = gs[q];
-            gs[q] = run;
-            run += v;
-        }
-    }
-    {
-        uint32_t dg[kItems];
-#pragma unroll
-        for (uint32_t j = 0; j < kItems; ++j) dg[j] = (key[j] >> shift) & (B - 1u);
-        rank_steps<BITS, true, kItems, RM>(&sm.cnt[w][0], dg, n > wbase ? n - wbase : 0u, rank, rflags);
-    }
-    __syncthreads();
-    uint32_t tot[PER], start[PER];
-    round_starts<BITS>(sm.cnt, reinterpret_cast<uint32_t*>(&sm.stage[0]), tot, start);
-    __syncthreads();
-#pragma unroll
-    for (uint32_t j = 0; j < kItems; ++j) {
-        if (wbase + j * 64u + lane < n) {
-            const uint32_t d = (key[j] >> shift) & (B - 1u);
-            sm.stage[packed_get(sm.cnt[w], d) + rank[j]] = make_uint2(key[j], idx[j]);
-        }
-    }
-    __syncthreads();
-    // publish the tile's per-digit counts (tile 0: inclusive at once), look back, publish the inclusive counts
-    const uint32_t lowmask = (1u << shift) - 1u;  // FINAL: shift >= 1 (a plan of >= 2 passes)
-    const uint32_t tag = (tick >> rbits) & 0xFFu;
-    unsigned long long* my = ring + ((size_t)(tick & rmask) << row_bits);
-    uint32_t mk[PER], excl[PER], mkw[PER];
-#pragma unroll
-    for (uint32_t q = 0; q < PER; ++q) {
-        const uint32_t d = threadIdx.x * PER + q;
-        mk[q] = (FINAL && d < B && tot[q]) ? sm.stage[start[q] + tot[q] - 1u].x & lowmask : 0u;
-        excl[q] = 0;
-        mkw[q] = 0;
-        if (d < B) __hip_atomic_store(my + d, sweep_word(tag, tile == 0 ? 2u : 1u, mk[q], tot[q]), __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (tile > 0 && tile < ntiles) {
-        bool done[PER], found[PER];
-        uint32_t back[PER];  // the next earlier tile to read is tile - back
-#pragma unroll
-        for (uint32_t q = 0; q < PER; ++q) {
-            done[q] = threadIdx.x * PER + q >= B;
-            found[q] = false;
-            back[q] = 1;
-        }
-        uint32_t spins = 0;
-        for (;;) {
-            bool open = false;
-#pragma unroll
-            for (uint32_t q = 0; q < PER; ++q) open |= !done[q];
-            if (!open) break;
-            unsigned long long v[PER][kSweepWin];
-#pragma unroll
-            for (uint32_t q = 0; q < PER; ++q) {
-                const uint32_t d = threadIdx.x * PER + q;
-#pragma unroll
-                for (uint32_t i = 0; i < kSweepWin; ++i) {
-                    const uint32_t bk = back[q] + i;
-                    v[q][i] = 0;
-                    if (!done[q] && bk <= tile)
-                        v[q][i] = __hip_atomic_load(ring + ((size_t)((tick - bk) & rmask) << row_bits) + d, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            bool moved = false;
-#pragma unroll
-            for (uint32_t q = 0; q < PER; ++q) {
-                if (done[q]) continue;
-                uint32_t used = 0;
-#pragma unroll
-                for (uint32_t i = 0; i < kSweepWin; ++i) {
-                    const uint32_t bk = back[q] + i;
-                    const unsigned long long x = v[q][i];
-                    const uint32_t kind = (uint32_t)(x >> 54) & 3u, tg = (uint32_t)(x >> 56);
-                    if (bk > tile || kind == 0u || tg != (((tick - bk) >> rbits) & 0xFFu)) break;  // unpublished: poll again
-                    const uint32_t c = (uint32_t)x;
-                    excl[q] += c;
-                    if (FINAL && !found[q] && c) {
-                        found[q] = true;
-                        mkw[q] = (uint32_t)(x >> 32) & kSweepMkMask;
-                    }
-                    ++used;
-                    if (kind == 2u) {
-                        done[q] = true;
-                        break;
-                    }
-                }
-                back[q] += used;
-                moved |= used != 0;
-            }
-            if (!moved) {
-                if (++spins > kSweepSpin) {  // cannot happen with every earlier tile started; never hang the GPU
-                    atomicOr(err_word, 1u);
-#pragma unroll
-                    for (uint32_t q = 0; q < PER; ++q) done[q] = true;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-    }
-    uint32_t* delta = &sm.cnt[0][0];  // the per-wave starts are consumed (the image is built)
-#pragma unroll
-    for (uint32_t q = 0; q < PER; ++q) {
-        const uint32_t d = threadIdx.x * PER + q;
-        if (d >= B) continue;
-        const uint32_t imk = tot[q] ? mk[q] : mkw[q];
-        if (tile > 0)
-            __hip_atomic_store(my + d, sweep_word(tag, 2u, imk, excl[q] + tot[q]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (FINAL && tile == ntiles - 1u) gmax[d] = imk;
-        delta[d] = gs[q] + excl[q] - start[q];
-        if (FINAL) sm.prev[d] = excl[q] ? (d << shift) | mkw[q] : (d << shift) - 1u;  // digit 0, none earlier: -1
-    }
-    __syncthreads();
-    const uint32_t cnt = tbase < n ? min(n - tbase, kTile) : 0u;
-#pragma unroll
-    for (uint32_t j = 0; j < kItems; ++j) {
-        const uint32_t i = j * 256u + threadIdx.x;
-        uint32_t len = 0, lo = 0, g = 0;
-        if (i < cnt) {
-            const uint2 kv = sm.stage[i];
-            const uint32_t d = (kv.x >> shift) & (B - 1u);
-            g = delta[d] + i;
-            if (g < n) {  // always, with consistent totals; keeps a corrupt input from writing out of bounds
-                if (!FINAL) {
-                    pair_out[g] = kv;
-                } else {
-                    order_out[g] = kv.y;
-                    uint32_t kp = sm.prev[d];
-                    if (i > 0) {
-                        const uint32_t pk = sm.stage[i - 1u].x;
-                        if (((pk >> shift) & (B - 1u)) == d) kp = pk;
-                    }
-                    lo = kp + 1u;                                  // buckets (kp, key] start at g
-                    len = kv.x - kp;                               // kp = -1: key + 1
-                    len = lo < nb ? min(len, nb - lo) : 0u;        // never past the offsets
-                }
-            }
-        }
-        if (FINAL) write_gap(offsets, lo, len, g, gap_q, gap_cap);
-    }
-    if (threadIdx.x == 0) {  // the last workgroup out moves the launch base on
-        __threadfence();
-        if (atomicAdd(&ctl[2], 1u) == gridDim.x - 1u) {
-            __hip_atomic_store(&ctl[1], __hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&ctl[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
-// After the FINAL sweep: the buckets past digit d's largest key (every bucket of an empty digit) start at the digit's end;
-// those past the last digit's range, up to nb - 1, at n.  One workgroup per digit; then the long-gap queue of write_gap
-// (k_offsets_long's work: grid-stride), and the last workgroup out empties the queue and zeroes every pass's digit totals
-// (gall, 3 << kMaxDigitBits words) for the next batch's k_digit_hist — no memset node, so a captured graph replays.
-__global__ __launch_bounds__(256) void k_sweep_tail(const uint32_t* __restrict__ gtot, const uint32_t* __restrict__ gmax,
-                                                    uint32_t bits, uint32_t shift, uint32_t nb, uint32_t* __restrict__ offsets,
-                                                    uint32_t* __restrict__ q, uint32_t cap, uint32_t* __restrict__ gall) {
-    __shared__ uint32_t last;
+// After the last pass and k_bound_apply: the buckets past digit d's largest key gmax[d] (every bucket of an empty digit)
+// start at the digit's end; those past the last digit's range, up to nb - 1, at n.  gtot: the last pass's digit totals.
+// One workgroup per digit; then the long-gap queue of write_gap (k_offsets_long's work: grid-stride), and the last
+// workgroup out empties the queue — no memset node, so a captured graph replays.
+__global__ __launch_bounds__(256) void k_offsets_tail(const uint32_t* __restrict__ gtot, const uint32_t* __restrict__ gmax,
+                                                      uint32_t bits, uint32_t shift, uint32_t nb, uint32_t* __restrict__ offsets,
+                                                      uint32_t* __restrict__ q, uint32_t cap) {
     __shared__ uint32_t wsum[kWaves];
     __shared__ uint32_t qn;
     const uint32_t B = 1u << bits, d = blockIdx.x;
@@ -2531,29 +2043,13 @@ __global__ __launch_bounds__(256) void k_sweep_tail(const uint32_t* __restrict__
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
-        last = atomicAdd(&q[1], 1u) == gridDim.x - 1u ? 1u : 0u;
-        if (last) {
+        if (atomicAdd(&q[1], 1u) == gridDim.x - 1u) {
             q[0] = 0;
             q[1] = 0;
         }
     }
-    __syncthreads();
-    if (last && gall)  // every workgroup has read its digit totals
-        for (uint32_t i = threadIdx.x; i < 3u << kMaxDigitBits; i += 256) gall[i] = 0;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// The LSD plan's bucket offsets without the sorted keys (round 6, VERDICT r5 item 3).  Its last pass (k_radix_pass
-// OUT_FINAL_GAPS) has each tile's image sorted by the whole key (the input is sorted by the lower digits, the pass is
-// stable), so it writes the buckets between consecutive keys of one digit inside the tile itself, and one row per tile of
-// FL[t][d] = each digit's first and last key's low 16 bits (the plan's last shift is <= 16 for this form).  What crosses
-// tiles — the buckets between the last key of digit d in the nearest earlier tile that has one and the first key of d in
-// tile t — is three column launches over the [tiles][2^bits] rows the pass already has (its counts C, its output bases M):
-//   k_bound_last   S[c][d] = the last key of d in chunk c of kScanRows tiles (kFlNone: no message of d there);
-//   k_bound_scan   P[c][d] = the last key of d in the chunks before c; gmax[d] = the last key of d overall;
-//   k_bound_apply  every tile with messages of d: offsets[(d << shift) + prev + 1, (d << shift) + first] = M[t][d];
-// then k_sweep_tail: the buckets past each digit's last key.  2 GB less traffic per 256M messages than writing the sorted
-// keys and reading them back (k_offsets_gaps), and every offset is still written exactly once.
 constexpr uint32_t kFlNone = 0xFFFFFFFFu;
 
 __device__ __forceinline__ bool fl_has(uint32_t fl) { return (fl & 0xFFFFu) <= (fl >> 16); }
@@ -2733,7 +2229,7 @@ __global__ __launch_bounds__(256) void k_bound_apply_t(const uint32_t* __restric
 // Stage 4, two-level path (keys of <= 22 bits; BucketPlan in orl_internal.h).  After the MSD pass the
 // messages are grouped by bucket b = key >> lb (stable), so each bucket is a contiguous range
 // [bstart[b], bstart[b+1]) in arrival order.  Buckets are cut into segments of <= seg messages; every segment
-// is counted (k_seg_count), the counts are column-scanned per bucket (k_seg_scan: segment bases inside the
+// is counted and the counts are column-scanned per bucket (k_seg_count_scan: segment bases inside the
 // bucket, and per-key totals = the bucket sizes of stage 4), one exclusive scan turns the per-key totals into
 // bucket offsets, and k_seg_scatter ranks each segment stably and writes `order`.  Without an MSD pass
 // (hb == 0) the whole batch is one bucket read straight from the activation handles.
@@ -2741,7 +2237,7 @@ __global__ __launch_bounds__(256) void k_bound_apply_t(const uint32_t* __restric
 // k_seg_plan: one workgroup; bstart = exclusive scan of the MSD column totals (or {0, n}), sstart = exclusive
 // scan of ceil(count / seg).  nbk <= 4096 buckets (2048 with 11-bit digits), four per thread.
 // sstart[kSkewSlot] = 1 when some bucket has more than kScanRows segments (a hot activation): the segment scan then
-// takes the chunked kernels, else the one-pass k_seg_scan (cheaper when every bucket is short).
+// takes the chunked kernels, else one workgroup per bucket (cheaper when every bucket is short).
 constexpr uint32_t kSkewSlot = 4097;
 
 template <uint32_t NT>
@@ -2831,18 +2327,12 @@ __device__ __forceinline__ bool seg_of_block(const uint32_t* __restrict__ bstart
     return true;
 }
 
-// IN_SOA8 / IN_SOA16: `in` = the MSD pass's index array [n_total], followed by its low-digit array (u8 / u16).
 template <int IN>
 __device__ __forceinline__ void seg_load(const void* __restrict__ in, uint32_t n_total, uint32_t e, uint32_t n_act, uint32_t& key,
                                          uint32_t& idx) {
     if (IN == IN_ACT) {
         key = bucket_key(ld_s4(static_cast<const uint32_t*>(in) + e), n_act);
         idx = e;
-    } else if (IN == IN_SOA8 || IN == IN_SOA16) {
-        const uint32_t* ix = static_cast<const uint32_t*>(in);
-        key = IN == IN_SOA8 ? (uint32_t) reinterpret_cast<const uint8_t*>(ix + n_total)[e]
-                            : (uint32_t) reinterpret_cast<const uint16_t*>(ix + n_total)[e];
-        idx = ix[e];
     } else {
         const uint2 v = ld_s4(static_cast<const uint2*>(in) + e);
         key = v.x;
@@ -2858,14 +2348,8 @@ __device__ __forceinline__ void seg_keys(const void* __restrict__ in, uint32_t n
     for (uint32_t j = 0; j < kItems; ++j) {
         const uint32_t e = c0 + j * 256u + threadIdx.x;
         const uint32_t ec = e < hi ? e : hi - 1;
-        if (IN == IN_SOA8 || IN == IN_SOA16) {  // the digit array only
-            const uint32_t* ix = static_cast<const uint32_t*>(in);
-            key[j] = IN == IN_SOA8 ? (uint32_t) reinterpret_cast<const uint8_t*>(ix + n_total)[ec]
-                                   : (uint32_t) reinterpret_cast<const uint16_t*>(ix + n_total)[ec];
-        } else {
-            uint32_t idx;
-            seg_load<IN>(in, n_total, ec, n_act, key[j], idx);
-        }
+        uint32_t idx;
+        seg_load<IN>(in, n_total, ec, n_act, key[j], idx);
     }
 }
 
@@ -2902,22 +2386,6 @@ __device__ __forceinline__ void seg_count_range(const void* __restrict__ in, uin
         seg_keys<IN>(in, n_total, n_act, c0, hi, key);
         seg_add<LB>(key, c0, hi, hist);
     }
-}
-
-template <int LB, int IN>
-__global__ __launch_bounds__(256) void k_seg_count(const void* __restrict__ in, uint32_t n_total, uint32_t n_act, uint32_t nbk,
-                                                   uint32_t seg, const uint32_t* __restrict__ bstart,
-                                                   const uint32_t* __restrict__ sstart, uint32_t* __restrict__ seg_hist) {
-    constexpr uint32_t BL = 1u << LB;
-    __shared__ uint32_t hist[BL];
-    SegRange r;
-    if (!seg_of_block(bstart, sstart, nbk, seg, r)) return;
-    for (uint32_t l = threadIdx.x; l < BL; l += 256) hist[l] = 0;
-    __syncthreads();
-    seg_count_range<LB, IN>(in, n_total, n_act, r.lo, r.hi, hist);
-    __syncthreads();
-    uint32_t* row = seg_hist + (size_t)r.index * BL;
-    for (uint32_t l = threadIdx.x; l < BL; l += 256) row[l] = hist[l];
 }
 
 __device__ __forceinline__ uint32_t bucket_of_segment(const uint32_t* __restrict__ sstart, uint32_t nbk, uint32_t j) {
@@ -3199,8 +2667,7 @@ __device__ __forceinline__ void seg_chunks(const void* __restrict__ in, uint32_t
 
 // Count and scan fused (round 4): for a plan without a skewed bucket (every bucket <= kScanRows segments) one workgroup
 // per bucket counts its segments in order and writes each segment's row as the exclusive prefix of the bucket's earlier
-// segments (what k_seg_scan made of k_seg_count's rows), then the bucket's per-key totals — no second pass over the
-// segment rows.  A skewed plan (k_col_apply's / k_seg_plan's device flag): without solo the launcher also sent k_seg_scan's
+// segments, then the bucket's per-key totals — no second pass over the segment rows.  A skewed plan (k_col_apply's / k_seg_plan's device flag): without solo the launcher also sent k_seg_scan's
 // chunked form and k_seg_carry, and this kernel only counts every segment (the workgroups striding over them); with solo
 // (the launcher, hinted by the previous plan's flag in skew_host, sent no segment scan) it takes seg_chunks above, in this
 // launch.  A stale hint therefore costs the look-back form's time, bounded (until round 5 it left a hot
@@ -3279,40 +2746,10 @@ __global__ __launch_bounds__(256, ORL_SEGCS_MINW) ORL_SEGCS_ATTR void k_seg_coun
     bucket_finish<LB>(hist, b, base, nb, nkeys, counts, direct, pick_word, wsum, wmax);
 }
 
-// Per bucket b and low digit l (every bucket has <= kScanRows segments): the segment rows become exclusive prefixes
-// inside the bucket and the column total (messages with key = b << lb | l) goes to counts[key] (keys < nb only).
-template <int LB>
-__device__ __forceinline__ void seg_scan_bucket(uint32_t* __restrict__ seg_hist, const uint32_t* __restrict__ sstart,
-                                                uint32_t nbk, uint32_t nb, uint32_t* __restrict__ counts, uint32_t b,
-                                                uint32_t l) {
-    constexpr uint32_t BL = 1u << LB;
-    if (b == 0 && l == 0)  // keys past the last bucket (at most one: n_act + 1 when n_act + 1 == 2^bits) hold nothing
-        for (uint32_t k = nbk << LB; k < nb; ++k) counts[k] = 0;
-    if (l >= BL) return;
-    const uint32_t j0 = sstart[b], j1 = sstart[b + 1];
-    uint32_t run = 0, j = j0;
-    for (; j + 4 <= j1; j += 4) {
-        uint32_t v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = seg_hist[(size_t)(j + q) * BL + l];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            seg_hist[(size_t)(j + q) * BL + l] = run;
-            run += v[q];
-        }
-    }
-    for (; j < j1; ++j) {
-        const uint32_t v = seg_hist[(size_t)j * BL + l];
-        seg_hist[(size_t)j * BL + l] = run;
-        run += v;
-    }
-    const uint32_t key = (b << LB) | l;
-    if (key < nb) counts[key] = run;
-}
-
-// The same scan, parallel over segments: a bucket of a hot activation (Zipf) has thousands of segments, which
-// k_seg_scan walks with one thread per column (278 us per call at config 3 on 8 ranks, ~1 ms on the hottest rank).
-// The segment rows are cut into chunks of kScanRows rows regardless of buckets:
+// The segment scan of a skewed plan, parallel over segments: a bucket of a hot activation (Zipf) has thousands of
+// segments, which a walk with one thread per column takes 278 us per call for at config 3 on 8 ranks, ~1 ms on the hottest
+// rank.  The segment rows (every segment's own counts, from k_seg_count_scan) are cut into chunks of kScanRows rows
+// regardless of buckets:
 //   seg_csum_chunk: per chunk and digit, exclusive prefixes inside the chunk restarting at every bucket start; the
 //                 sum of the bucket still open at the chunk's end -> carry[c][l]; buckets ending inside the chunk
 //                 write their (possibly partial) total to counts[key]; buckets without segments get 0;
@@ -3320,8 +2757,8 @@ __device__ __forceinline__ void seg_scan_bucket(uint32_t* __restrict__ seg_hist,
 //                 acc -> A*acc + B, A in {0, 1}): carry[c][l] becomes the chunk's carry-in, added to the total of the
 //                 chunk's first bucket when that bucket ends inside the chunk;
 //   k_seg_scatter adds the carry-in to the row base of every segment of a chunk's first bucket.
-// k_seg_plan flags the skew on the device, so both forms are launched and the one not taken returns at once: the
-// short-bucket form shares k_seg_scan's launch, and k_seg_carry exits.
+// k_seg_plan flags the skew on the device, so k_seg_scan and k_seg_carry are launched for every plan that may be skewed
+// and return at once for one that is not (k_seg_count_scan has scanned its rows already).
 // Each thread loads 16 rows at a time (all in flight) before it rewrites them.
 
 template <int LB>
@@ -3375,17 +2812,15 @@ __device__ __forceinline__ void seg_csum_chunk(uint32_t* __restrict__ seg_hist, 
     carry[(size_t)c * BL + l] = run;
 }
 
-// One launch for both forms: grid (max(nbk, chunks), ceil(BL / 256)); k_seg_plan's skew flag picks the role.
+// grid (chunks, ceil(BL / 256)).  Without k_seg_plan's skew flag k_seg_count_scan already wrote the prefixed rows and the
+// counts.
 template <int LB>
 __global__ __launch_bounds__(256) void k_seg_scan(uint32_t* __restrict__ seg_hist, const uint32_t* __restrict__ sstart,
                                                   uint32_t nbk, uint32_t nb, uint32_t* __restrict__ carry,
-                                                  uint32_t* __restrict__ meta, uint32_t* __restrict__ counts, uint32_t fused) {
+                                                  uint32_t* __restrict__ meta, uint32_t* __restrict__ counts) {
+    if (!sstart[kSkewSlot]) return;
     const uint32_t l = blockIdx.y * 256u + threadIdx.x;
-    if (!sstart[kSkewSlot]) {  // (fused: k_seg_count_scan already wrote the prefixed rows and the counts)
-        if (!fused && blockIdx.x < nbk) seg_scan_bucket<LB>(seg_hist, sstart, nbk, nb, counts, blockIdx.x, l);
-    } else {
-        seg_csum_chunk<LB>(seg_hist, sstart, nbk, nb, carry, meta, counts, blockIdx.x, l);
-    }
+    seg_csum_chunk<LB>(seg_hist, sstart, nbk, nb, carry, meta, counts, blockIdx.x, l);
 }
 
 // 16 digits per block, 16 threads per digit, each owning a contiguous run of chunks: the run's composed map, a scan of
@@ -3494,7 +2929,7 @@ __global__ __launch_bounds__(256) void k_seg_scatter(const void* __restrict__ in
     uint32_t run[PER];  // global position of the next message with digit threadIdx.x * PER + q
     const uint32_t* hrow = seg_hist + (size_t)r.index * BL;
     // a hot bucket's segments (a skewed plan): the carry-in of the chunk of `crow` rows (k_seg_count_scan's kLbRows, or the
-    // legacy k_seg_scan's kScanRows) whose first bucket this segment is in
+    // k_seg_scan's kScanRows) whose first bucket this segment is in
     const uint32_t ch = r.index / crow;
     const uint32_t cin_on = (sstart[kSkewSlot] && (seg_meta[ch] & kMetaBucket) == r.bucket) ? 1u : 0u;
     const uint32_t* cin_row = seg_carry + (cin_on ? (size_t)ch * BL : 0);
@@ -4903,15 +4338,9 @@ uint32_t route_items(uint64_t n, uint32_t max_items, uint32_t min_wg = 0) {
 }
 
 // The LSD plan's later passes in 3072-element tiles (round 6): their LDS image is 24 KB instead of 32, so 6 workgroups fit a
-// CU instead of 4 (the first pass keeps 4096: its rows are the route kernel's).  ORL_LSD_TILE12=0: 4096 (A/B).
+// CU instead of 4 (the first pass keeps 4096: its rows are the route kernel's): config 3 6.94 -> 6.90 ms
+// (profiles/r06t12_lsd_tile12_ab.txt).
 constexpr uint32_t kItems12 = 12;
-bool lsd_tile12() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_LSD_TILE12");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
 
 template <int BITS>
 void launch_pass_bits(int rm, int in, int out, const void* kin, uint32_t n, uint32_t n_act, uint32_t shift, const uint32_t* toff,
@@ -4928,8 +4357,6 @@ void launch_pass_bits(int rm, int in, int out, const void* kin, uint32_t n, uint
         switch (out) {
             case OUT_PAIR: ORL_RP(IN_ACT, OUT_PAIR, kMsdItems); break;
             case OUT_PAIR_SMALL: ORL_RP(IN_ACT, OUT_PAIR, kMsdItemsSmall); break;
-            case OUT_SOA8: ORL_RP(IN_ACT, OUT_SOA8, kMsdItems); break;
-            case OUT_SOA16: ORL_RP(IN_ACT, OUT_SOA16, kMsdItems); break;
             case OUT_LSD_PAIR: ORL_RP(IN_ACT, OUT_PAIR, kItems); break;
             case OUT_PAIR_DIG: ORL_RP(IN_ACT, OUT_PAIR_DIG, kItems); break;
             default: ORL_RP(IN_ACT, OUT_FINAL, kItems); break;
@@ -4964,61 +4391,6 @@ void launch_pass(int rm, int bits, int in, int out, const void* kin, uint32_t n,
     }
 }
 
-// The LSD plan's single-sweep passes (k_sweep, round 6): on when the context holds the look-back ring (ORL_LSD_SWEEP=1 at
-// context creation; off by default: 7 ms per pass against 0.85 ms, see k_sweep).
-bool lsd_sweep(const Scratch& s) { return s.sw_ring != nullptr; }
-
-template <int BITS>
-void launch_sweep_bits(int rm, int in, bool fin, const void* kin, uint32_t n, uint32_t n_act, uint32_t shift, const uint32_t* gtot,
-                       uint32_t ntiles, uint2* pout, uint32_t* order, uint32_t* offsets, uint32_t nb, const Scratch& s,
-                       hipStream_t st) {
-#define ORL_SW3(I, F, R) hipLaunchKernelGGL((k_sweep<BITS, I, F, R>), dim3(ntiles), dim3(256), 0, st, kin, n, n_act, shift, gtot,   \
-                                            s.sw_ring, s.sw_rbits, s.sw_row_bits, s.sw_ctl, ntiles, pout, order, offsets, nb,        \
-                                            s.sw_gmax, s.gap_q, s.gap_cap, s.s4_err)
-#define ORL_SW(I, F) do { if (rm == kRmPlain) ORL_SW3(I, F, kRmPlain); else if (rm == kRmHot) ORL_SW3(I, F, kRmHot);                    \
-                          else ORL_SW3(I, F, kRmBallot); } while (0)
-    if (in == IN_ACT) ORL_SW(IN_ACT, false);  // a plan of >= 2 passes: the handles are never the last pass's input
-    else if (fin) ORL_SW(IN_PAIR, true);
-    else ORL_SW(IN_PAIR, false);
-#undef ORL_SW
-#undef ORL_SW3
-}
-
-// The LSD plan's stage 4: one digit-total read of the handles, then the passes act → pairs_a → pairs_b → ... → (order,
-// offsets), then the offsets' tails.  7 + 4 launches fewer than the k_hist_pairs form for three passes, no sorted keys.
-int bucket_lsd_sweep(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32_t* d_order, uint32_t* d_offsets,
-                     const Scratch& s, hipStream_t st) {
-    const RadixPlan plan = make_bucket_plan(n_act).lsd;
-    const uint32_t nb = n_act + 2, ntiles = ceil_div(n, kTile);
-    if (plan.passes < 2 || plan.passes > 3) return (int)hipErrorInvalidValue;  // the context allocated no ring for it
-    uint32_t sh[3] = {0, 0, 0}, mk[3] = {0, 0, 0};
-    for (int p = 0; p < plan.passes; ++p) {
-        sh[p] = (uint32_t)plan.shift[p];
-        mk[p] = (1u << plan.bits[p]) - 1u;
-    }
-    hipLaunchKernelGGL(k_digit_hist, dim3(std::min<uint32_t>(ceil_div(n, 256u * 16u), 1024u)), dim3(256), 0, st, d_act, n, n_act,
-                       (uint32_t)plan.passes, sh[0], sh[1], sh[2], mk[0], mk[1], mk[2], s.sw_gtot);
-    const int rm = host_rm(s.device);
-    uint2* pbuf[2] = {s.pairs_a, s.pairs_b};
-    for (int p = 0; p < plan.passes; ++p) {
-        const bool last = p == plan.passes - 1;
-        const void* kin = p == 0 ? static_cast<const void*>(d_act) : static_cast<const void*>(pbuf[(p - 1) & 1]);
-        const uint32_t* gtot = s.sw_gtot + ((size_t)p << kMaxDigitBits);
-        const int in = p == 0 ? IN_ACT : IN_PAIR;
-        switch (plan.bits[p]) {
-#define ORL_CASE(B) case B: launch_sweep_bits<B>(rm, in, last, kin, n, n_act, (uint32_t)plan.shift[p], gtot, ntiles, pbuf[p & 1], \
-                                                 d_order, d_offsets, nb, s, st); break;
-            ORL_CASE(7) ORL_CASE(8) ORL_CASE(9) ORL_CASE(10) ORL_CASE(11)
-#undef ORL_CASE
-            default: return (int)hipErrorInvalidValue;  // 3 passes of > 22 bits: 7-11 bits each
-        }
-    }
-    const int lp = plan.passes - 1;
-    hipLaunchKernelGGL(k_sweep_tail, dim3(1u << plan.bits[lp]), dim3(256), 0, st, s.sw_gtot + ((size_t)lp << kMaxDigitBits), s.sw_gmax,
-                       (uint32_t)plan.bits[lp], (uint32_t)plan.shift[lp], nb, d_offsets, s.gap_q, s.gap_cap, s.sw_gtot);
-    return (int)hipGetLastError();
-}
-
 // Column scan of a tile-major [ntiles][bins] u16 count matrix C (s.tile_cnt) into per-(tile, bin) u32 output bases M.
 // row_step: the reading pass uses rows t % row_step == 0 only.
 // plan_n > 0: the two-level plan's MSD columns — the apply kernel also writes the segment plan (k_seg_plan's work) for
@@ -5048,14 +4420,11 @@ struct RouteHist {
     uint32_t bins, shift;
 };
 
-RouteHist route_hist(uint32_t n_act, const Scratch& s) {
+RouteHist route_hist(uint32_t n_act) {
     const BucketPlan bp = make_bucket_plan(n_act);
     if (bp.two_level) return {bp.hb > 0, 1u << bp.hb, (uint32_t)bp.lb};
-    if (lsd_sweep(s)) return {false, 1u, 0u};  // the single-sweep passes count their digits themselves (k_digit_hist)
     return {true, 1u << bp.lsd.bits[0], (uint32_t)bp.lsd.shift[0]};
 }
-
-bool seg_fused();
 
 // Launch epoch of the fused level-2 kernel's look-back flags (1 .. 2^30 - 1, never 0: the flag words start zeroed).
 uint32_t next_seg_epoch(const Scratch& s) {
@@ -5070,10 +4439,9 @@ void launch_seg_bits(int in, const void* kin, uint32_t n, uint32_t n_act, uint32
     const uint32_t nb = n_act + 2;
     // the fused count + scan (one workgroup per bucket) serves every plan.  solo: the last plan had no skewed bucket, so no
     // segment scan is launched; a skewed plan then takes the fused kernel's chunked look-back form (the hint can be stale:
-    // bounded cost, never wrong).  Otherwise the fused kernel only counts a skewed plan's segments and k_seg_scan's chunked
-    // form + k_seg_carry scan them (its unskewed form does nothing).  ORL_SEG_FUSED=0: k_seg_count + k_seg_scan always.
-    const uint32_t fz = seg_fused() ? 1u : 0u;
-    const uint32_t solo = fz && s.hot_host && !__atomic_load_n(s.hot_host + 1, __ATOMIC_ACQUIRE) ? 1u : 0u;
+    // bounded cost, never wrong).  Otherwise the fused kernel only counts a skewed plan's segments and k_seg_scan +
+    // k_seg_carry scan them (both return at once for an unskewed plan).
+    const uint32_t solo = s.hot_host && !__atomic_load_n(s.hot_host + 1, __ATOMIC_ACQUIRE) ? 1u : 0u;
     // direct: nor an offsets scan (not with the hot-key path)
     const uint32_t direct = solo && !hot ? 1u : 0u;
     // direct with the pick: k_seg_count_scan folds the per-bucket maxima, k_seg_scatter stores the next batch's key
@@ -5086,28 +4454,20 @@ void launch_seg_bits(int in, const void* kin, uint32_t n, uint32_t n_act, uint32
 #define ORL_SF(I) hipLaunchKernelGGL((k_seg_count_scan<LB, I>), dim3(fgrid), dim3(256), 0, st, kin, n, n_act, nbk, nb, seg, s.bstart, \
                                      s.sstart, s.seg_hist, d_offsets, solo, direct, skew_host, pick_word, n_act + 1, s.seg_carry,  \
                                      s.seg_meta, s.seg_lb, s.seg_lbctl, s.seg_lb_cap, epoch, s.s4_err)
-#define ORL_SC(I) hipLaunchKernelGGL((k_seg_count<LB, I>), dim3(grid), dim3(256), 0, st, kin, n, n_act, nbk, seg, s.bstart, s.sstart, \
-                                     s.seg_hist)
 #define ORL_SS3(I, R) hipLaunchKernelGGL((k_seg_scatter<LB, I, R>), dim3(grid), dim3(256), 0, st, kin, n, n_act, nbk, seg, s.bstart,\
                                          s.sstart, s.seg_hist, d_offsets, nb, n, s.seg_carry, s.seg_meta, d_order,         \
                                          solo ? kLbRows : kScanRows,                                                         \
                                          pick_word, next_key, s.hot_host_dev)
 #define ORL_SS(I) do { const int rm_ = host_rm(s.device); if (rm_ == kRmPlain) ORL_SS3(I, kRmPlain); else if (rm_ == kRmHot)             \
                            ORL_SS3(I, kRmHot); else ORL_SS3(I, kRmBallot); } while (0)
-    if (fz) {
-        if (in == IN_ACT) ORL_SF(IN_ACT); else if (in == IN_PAIR) ORL_SF(IN_PAIR);
-        else if (in == IN_SOA8) ORL_SF(IN_SOA8); else ORL_SF(IN_SOA16);
-    } else {
-        if (in == IN_ACT) ORL_SC(IN_ACT); else if (in == IN_PAIR) ORL_SC(IN_PAIR);
-        else if (in == IN_SOA8) ORL_SC(IN_SOA8); else ORL_SC(IN_SOA16);
-    }
-    // the segment scan: k_seg_scan when every bucket has <= kScanRows segments, else the chunked kernels (k_seg_plan
-    // sets the flag on the device; the path not taken returns at once)
+    if (in == IN_ACT) ORL_SF(IN_ACT); else ORL_SF(IN_PAIR);
+    // the segment scan of a skewed plan, in chunks of kScanRows segments (k_seg_plan sets the flag on the device; without
+    // it both kernels return at once)
     const uint32_t cb = ceil_div(1u << LB, 256);
     const uint32_t nch = ceil_div(grid, kScanRows);
     if (!solo) {
-        hipLaunchKernelGGL((k_seg_scan<LB>), dim3(std::max(nbk, nch), cb), dim3(256), 0, st, s.seg_hist, s.sstart, nbk, nb,
-                           s.seg_carry, s.seg_meta, d_offsets, fz);
+        hipLaunchKernelGGL((k_seg_scan<LB>), dim3(nch, cb), dim3(256), 0, st, s.seg_hist, s.sstart, nbk, nb,
+                           s.seg_carry, s.seg_meta, d_offsets);
         hipLaunchKernelGGL((k_seg_carry<LB>), dim3(ceil_div(1u << LB, 16)), dim3(256), 0, st, s.sstart, nbk, nb, s.seg_meta,
                            s.seg_carry, d_offsets);
     }
@@ -5119,13 +4479,11 @@ void launch_seg_bits(int in, const void* kin, uint32_t n, uint32_t n_act, uint32
         s.hot_parity ^= 1u;
     else if (!direct)
         scan_inplace(d_offsets, nb, s, st);
-    if (in == IN_ACT) ORL_SS(IN_ACT); else if (in == IN_PAIR) ORL_SS(IN_PAIR);
-    else if (in == IN_SOA8) ORL_SS(IN_SOA8); else ORL_SS(IN_SOA16);
+    if (in == IN_ACT) ORL_SS(IN_ACT); else ORL_SS(IN_PAIR);
     if (hot)  // the hot run's copy (this batch's key: hw)
         hipLaunchKernelGGL(k_hot_tail, dim3(std::min<uint32_t>(ceil_div(n / 4u, 256u * kTailUnroll), 2048u)), dim3(256), 0, st,
                            hw, s.col_tot + nbk, n, n_act + 1, s.sorted_keys, d_offsets, d_order);
 #undef ORL_SF
-#undef ORL_SC
 #undef ORL_SS
 #undef ORL_SS3
 }
@@ -5141,106 +4499,28 @@ void launch_seg(int lb, int in, const void* kin, uint32_t n, uint32_t n_act, uin
     }
 }
 
-// Level-2 input layout of the two-level path: {key, index} pairs, or (ORL_STAGE4_SOA=1) SoA — indices + the low digit
-// only.  SoA cuts level 2's bytes (k_seg_count 130 -> 38 us at config 2) but the MSD pass's narrow scattered digit stores
-// double its write requests (221 -> 330 us): a wash, measured in profiles/r02_stage4_ab.txt, so pairs stay the default.
-bool stage4_soa() {
-    static const bool soa = [] {
-        const char* e = getenv("ORL_STAGE4_SOA");
-        return e && e[0] == '1';
-    }();
-    return soa;
-}
-
-// Level 2's count and segment scan fused for plans without a skewed bucket (k_seg_count_scan); ORL_SEG_FUSED=0 keeps the
-// two-kernel form for every plan (A/B).
-// A small fan-out batch's column chunk sums accumulated by the fan-out kernel (round 5); ORL_COL_SELF=0: k_col_sum (A/B).
-bool col_self() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_COL_SELF");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-bool seg_fused() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_SEG_FUSED");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// LSD path's bucket offsets written by the last pass and k_bound_* (round 6); ORL_LSD_FUSED_OFFSETS=0: the sorted keys +
-// k_offsets_gaps (A/B).
-bool lsd_fused_offsets() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_LSD_FUSED_OFFSETS");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// LSD path's bucket offsets: ORL_OFFSETS_SUFMIN=1 keeps the round-2 five-launch form (A/B).
-bool offsets_sufmin() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_OFFSETS_SUFMIN");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
-
-// The fused offsets' bound kernels with LDS-staged rows (k_bound_*_t); ORL_BOUND_STAGED=0: column loads (A/B).
-bool bound_staged() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_BOUND_STAGED");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// The digit stream's histogram, one wave per tile (k_hist_dig8_wave); ORL_DIG8_WAVE=0: one workgroup per tile (A/B).
-bool dig8_wave() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_DIG8_WAVE");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// LSD passes hand the next pass its digit as a byte stream (OUT_PAIR_DIG) when it has <= 8 bits; ORL_LSD_DIGITS=0: the next
-// histogram reads the pairs (A/B).
-bool lsd_digits() {
-    static const bool on = [] {
-        const char* e = getenv("ORL_LSD_DIGITS");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// The hot-key path (kNoHotKey) runs on batches of >= kHotMinBatch messages of the two-level plan with an MSD pass and pair
-// layout; ORL_NO_HOT=1 turns it off (A/B).
 // The LSD plan's last pass writes the bucket offsets itself (OUT_FINAL_GAPS) when its keys' low part fits the 16-bit halves
 // of FL and the batch is dense in buckets (>= 2 messages per bucket): config 3 (16 per bucket) 7.77 -> 7.62 ms, but config 4
 // (0.7 per bucket: most of 10M offsets are gaps that cross tiles, k_bound_apply's share) 0.392 -> 0.436 ms, where
 // k_offsets_gaps' LDS spans stay faster (profiles/r06m_config4_lsd_ab.txt).
 bool lsd_gaps(const RadixPlan& plan, uint64_t n, uint32_t n_act) {
-    return lsd_fused_offsets() && !offsets_sufmin() && plan.shift[plan.passes - 1] <= 16 && n >= 2ull * (n_act + 2ull);
+    return plan.shift[plan.passes - 1] <= 16 && n >= 2ull * (n_act + 2ull);
 }
 
+// The hot-key path (kNoHotKey) runs on batches of >= kHotMinBatch messages of the two-level plan with an MSD pass;
+// ORL_NO_HOT=1 turns it off (A/B).
 bool hot_path_on(uint64_t n, uint32_t n_act, const Scratch& s) {
     static const bool off = [] {
         const char* e = getenv("ORL_NO_HOT");
         return e && e[0] == '1';
     }();
-    if (off || !s.hot || n < kHotMinBatch || stage4_soa()) return false;
+    if (off || !s.hot || n < kHotMinBatch) return false;
     const BucketPlan bp = make_bucket_plan(n_act);
     if (bp.two_level) return bp.hb > 0;
     // the LSD plan's hot-key path: opt-in (ORL_LSD_HOT=1 at context creation allocates s.lsd_hot), measured slower at
     // config 3 (7.22 -> 7.28 ms, profiles/r06t_lsd_hot_ab.txt): the hot key's elements are the cheapest ones of an LSD
     // pass (long one-digit runs, coalesced stores), so skipping them saves less than the run, the fix-up and the pick cost
-    return s.lsd_hot && !lsd_sweep(s) && lsd_gaps(bp.lsd, n, n_act);
+    return s.lsd_hot && lsd_gaps(bp.lsd, n, n_act);
 }
 
 // Whether the last pick (the tail kernel of an earlier batch, mirrored to mapped host memory) found a hot key: a batch
@@ -5252,8 +4532,10 @@ bool hot_known(const Scratch& s) {
 }
 
 // Stage 4 after a route kernel that already wrote route_hist()'s tile histogram into s.tile_hist.
-//   two-level: [MSD pass by the high digit → pairs_a] → segment count → segment scan → offsets scan → scatter;
-//   LSD fallback: passes act → pairs_a → pairs_b → ... → (order, sorted keys); offsets from the sorted keys.
+//   two-level: [MSD pass by the high digit → pairs_a] → segment count + scan → [offsets scan] → scatter;
+//   LSD fallback: passes act → pairs_a → pairs_b → ... → order, each later pass after a histogram of its digit (from the
+//   previous pass's digit stream when the digit has <= 8 bits, else from the pairs); the offsets from the last pass itself
+//   + k_bound_* + k_offsets_tail on a dense batch (lsd_gaps), else from the sorted keys (k_offsets_gaps).
 // hot: the histogram pass wrote the hot key's per-row counts (s.hot_rows): this batch takes the hot-key path.  pick: the
 // batch is large enough for the path: the tail kernel picks the next batch's key (hot implies pick).
 int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32_t route_items, uint32_t* d_order,
@@ -5265,7 +4547,7 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
     // pass 0's histogram rows were written by the route kernel, one per route tile of 256 * route_items
     const uint32_t nrows0 = ceil_div(n, kRouteThreads * route_items);
     if (bp.two_level) {
-        const uint32_t mitems = stage4_soa() ? kMsdItems : msd_items(n, route_items);
+        const uint32_t mitems = msd_items(n, route_items);
         const uint32_t row_step0 = mitems / route_items;
         const uint32_t ntiles = ceil_div(n, kRouteThreads * mitems);
         const uint32_t nbk = 1u << bp.hb;
@@ -5274,24 +4556,16 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
         const void* kin = d_act;
         if (bp.hb > 0) {
             col_scan(s.tile_hist, nrows0, nbk, row_step0, s, st, hot ? s.hot_rows : nullptr, n, seg, self_cols);  // + the segment plan
-            if (stage4_soa()) {  // the MSD pass writes level 2's input as SoA: indices, then the low digits only (u8 / u16)
-                uint32_t* idx = reinterpret_cast<uint32_t*>(s.pairs_a);
-                launch_pass(host_rm(s.device), bp.hb, IN_ACT, bp.lb <= 8 ? OUT_SOA8 : OUT_SOA16, d_act, n, n_act, (uint32_t)bp.lb, s.tile_hist,
-                            row_step0, ntiles, nullptr, idx, idx + n, st);
-            } else {
-                launch_pass(host_rm(s.device), bp.hb, IN_ACT, mitems == kMsdItems ? OUT_PAIR : OUT_PAIR_SMALL, d_act, n, n_act, (uint32_t)bp.lb, s.tile_hist,
-                            row_step0, ntiles, s.pairs_a, nullptr, nullptr, st, hot ? hot_cur(s) : nullptr, hot ? s.hot_rows : nullptr,
-                            hot ? s.sorted_keys : nullptr);
-            }
+            launch_pass(host_rm(s.device), bp.hb, IN_ACT, mitems == kMsdItems ? OUT_PAIR : OUT_PAIR_SMALL, d_act, n, n_act, (uint32_t)bp.lb, s.tile_hist,
+                        row_step0, ntiles, s.pairs_a, nullptr, nullptr, st, hot ? hot_cur(s) : nullptr, hot ? s.hot_rows : nullptr,
+                        hot ? s.sorted_keys : nullptr);
             kin = s.pairs_a;
         }
         if (bp.hb == 0)  // one bucket: {0, n} (with an MSD pass, k_col_apply wrote the plan)
             hipLaunchKernelGGL(k_seg_plan, dim3(1), dim3(1024), 0, st, nullptr, nbk, n, seg, s.bstart, s.sstart);
-        const int lin = bp.hb == 0 ? IN_ACT : !stage4_soa() ? IN_PAIR : bp.lb <= 8 ? IN_SOA8 : IN_SOA16;
-        launch_seg(bp.lb, lin, kin, n, n_act, nbk, seg, grid, d_order, d_offsets, s, st, hot && bp.hb > 0, (hot || pick) && bp.hb > 0);
+        launch_seg(bp.lb, bp.hb == 0 ? IN_ACT : IN_PAIR, kin, n, n_act, nbk, seg, grid, d_order, d_offsets, s, st, hot && bp.hb > 0, (hot || pick) && bp.hb > 0);
         return (int)hipGetLastError();
     }
-    if (lsd_sweep(s)) return bucket_lsd_sweep(d_act, n, n_act, d_order, d_offsets, s, st);
     const RadixPlan& plan = bp.lsd;
     const uint32_t row_step0 = kItems / route_items;
     const bool gaps = lsd_gaps(plan, n, n_act);
@@ -5305,7 +4579,7 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
     uint8_t* dig = reinterpret_cast<uint8_t*>(s.sorted_keys);
     bool have_dig = false;
     // the later passes in 3072-element tiles when each of them gets its digit stream and writes the offsets itself
-    bool t12 = lsd_tile12() && gaps && lsd_digits() && dig8_wave() && plan.passes >= 2;
+    bool t12 = gaps && plan.passes >= 2;
     for (int p = 1; p < plan.passes; ++p) t12 = t12 && plan.bits[p] <= 8;
     const uint32_t ntiles12 = ceil_div(n, kRouteThreads * kItems12);
     const uint32_t ntl = t12 ? ntiles12 : ntiles;  // the later passes' tiles
@@ -5318,20 +4592,17 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
         if (p > 0 && t12)
             hipLaunchKernelGGL((k_hist_dig8_wave<3, 1>), dim3(ceil_div(ntl, kWaves)), dim3(256), 0, st, dig, n, bins, ntl,
                                s.tile_cnt, n_dev);
-        else if (p > 0 && have_dig && bins >= 2 && bins <= 256 && dig8_wave())
+        else if (p > 0 && have_dig)  // a digit stream has 1 to 8 bits (wdig): 2 <= bins <= 256
             hipLaunchKernelGGL((k_hist_dig8_wave<4, 1>), dim3(ceil_div(ntiles, kWaves)), dim3(256), 0, st, dig, n, bins, ntiles,
                                s.tile_cnt, n_dev);
-        else if (p > 0 && have_dig)
-            hipLaunchKernelGGL((k_hist_pairs<false, true>), dim3(ntiles), dim3(256), 0, st, dig, n, n_act, 0u, bins, s.tile_cnt,
-                               nullptr, nullptr, n_dev);
-        else if (p > 0)
+        else if (p > 0)  // a digit of more than 8 bits: from the pairs
             hipLaunchKernelGGL(k_hist_pairs<false>, dim3(ntiles), dim3(256), 0, st, pbuf[(p - 1) & 1], n, n_act,
                                (uint32_t)plan.shift[p], bins, s.tile_cnt, nullptr, nullptr, n_dev);
         col_scan(s.tile_hist, nrows, bins, row_step, s, st, (p == 0 && lhot) ? s.hot_rows : nullptr, 0, 0, p == 0 && self_cols);
         if (p == 0 && lhot)  // {hot key, hc, n - hc} before the later passes' column scans reuse col_tot
             hipLaunchKernelGGL(k_lsd_hot_prep, dim3(1), dim3(64), 0, st, hw, s.col_tot + bins, n, s.lsd_hot);
         const bool last = p == plan.passes - 1;
-        const bool wdig = !last && lsd_digits() && plan.bits[p + 1] <= 8;
+        const bool wdig = !last && plan.bits[p + 1] <= 8;
         const void* kin = (p == 0) ? static_cast<const void*>(d_act) : static_cast<const void*>(pbuf[(p - 1) & 1]);
         const int out = !last ? (wdig ? OUT_PAIR_DIG : OUT_LSD_PAIR) : gaps ? OUT_FINAL_GAPS : OUT_FINAL;
         const uint32_t dsel = wdig ? (uint32_t)plan.shift[p + 1] | ((uint32_t)plan.bits[p + 1] << 8) : 0u;
@@ -5346,7 +4617,7 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
         const int lp = plan.passes - 1;
         const uint32_t ntiles = ntl;  // the last pass's tiles
         const uint32_t bins = 1u << plan.bits[lp], nch = ceil_div(ntiles, kScanRows);
-        const bool bt = bins % kBoundCols == 0 && bound_staged();
+        const bool bt = bins % kBoundCols == 0;  // the forms with LDS-staged rows (profiles/r06y_bound_staged_ab.txt)
         if (bt) hipLaunchKernelGGL(k_bound_last_t, dim3(nch), dim3(256), 0, st, s.sorted_keys, ntiles, bins, s.col_sums);
         else hipLaunchKernelGGL(k_bound_last, dim3(nch), dim3(256), 0, st, s.sorted_keys, ntiles, bins, s.col_sums);
         hipLaunchKernelGGL(k_bound_scan, dim3(ceil_div(bins, kColScanCols)), dim3(256), 0, st, s.col_sums, nch, bins,
@@ -5357,8 +4628,8 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
         else
             hipLaunchKernelGGL(k_bound_apply, dim3(nch), dim3(256), 0, st, s.sorted_keys, s.tile_hist, s.col_sums, ntiles, bins,
                                (uint32_t)plan.shift[lp], nb, d_offsets, s.gap_q, s.gap_cap);
-        hipLaunchKernelGGL(k_sweep_tail, dim3(bins), dim3(256), 0, st, s.col_tot, s.sorted_keys + (size_t)ntiles * bins,
-                           (uint32_t)plan.bits[lp], (uint32_t)plan.shift[lp], nb, d_offsets, s.gap_q, s.gap_cap, nullptr);
+        hipLaunchKernelGGL(k_offsets_tail, dim3(bins), dim3(256), 0, st, s.col_tot, s.sorted_keys + (size_t)ntiles * bins,
+                           (uint32_t)plan.bits[lp], (uint32_t)plan.shift[lp], nb, d_offsets, s.gap_q, s.gap_cap);
         if (lhot) {  // the offsets above the hot key + hc, then its run into the gap the last pass left
             hipLaunchKernelGGL(k_lsd_hot_fix, dim3(std::min<uint32_t>(ceil_div(nb, 256u * 16u), 2048u)), dim3(256), 0, st, d_offsets,
                                nb, s.lsd_hot);
@@ -5372,15 +4643,6 @@ int bucket_after_route(const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32
                                s.hot_host_dev);
             s.hot_parity ^= 1u;
         }
-        return (int)hipGetLastError();
-    }
-    if (offsets_sufmin()) {  // A/B: the five-launch form (fill, mark, suffix minima)
-        hipLaunchKernelGGL(k_fill_u32, dim3(ceil_div(nb, 256)), dim3(256), 0, st, d_offsets, nb, kNoOffset);
-        hipLaunchKernelGGL(k_offsets_mark, dim3(ceil_div(ceil_div(n, 16), 256)), dim3(256), 0, st, s.sorted_keys, n, nb, d_offsets);
-        const uint32_t nch = ceil_div(nb, kScanChunk);
-        hipLaunchKernelGGL(k_sufmin_reduce, dim3(nch), dim3(256), 0, st, d_offsets, nb, s.scan_sums);
-        hipLaunchKernelGGL(k_sufmin_chunks, dim3(1), dim3(256), 0, st, s.scan_sums, nch, n);
-        hipLaunchKernelGGL(k_sufmin_down, dim3(nch), dim3(256), 0, st, d_offsets, nb, s.scan_sums);
         return (int)hipGetLastError();
     }
     // every bucket written once from the gaps between consecutive sorted keys (positions 0..n: n + 1 of them)
@@ -5473,7 +4735,7 @@ int launch_route_bucket(const RouteParams* d_params, const DirView& dv, const vo
     }
     const uint32_t items = route_items(n, max_route_items(n_act));
     const uint32_t nwg = ceil_div(n, kRouteThreads * items);
-    const RouteHist rh = route_hist(n_act, s);
+    const RouteHist rh = route_hist(n_act);
     if (ev_begin) (void)hipEventRecord((hipEvent_t)ev_begin, st);
     const bool hist = buckets && rh.on;
     const bool pick = hist && hot_path_on(n, n_act, s);
@@ -5552,9 +4814,9 @@ int launch_fanout_route_bucket(const RouteParams* d_params, const DirView& dv, c
     const uint32_t nbs = ceil_div(m, small ? kScanSmallChunk : kScanChunk);
     // a small batch (at most kSelfScanChunks 64-row chunks of fan-out tiles, bounded by max_out): the fan-out kernel adds
     // its tiles' counts into s.col_sums, which the degree scan zeroes first (no k_col_sum launch)
-    const RouteHist rh = route_hist(n_act, s);
+    const RouteHist rh = route_hist(n_act);
     const uint64_t nch_max = ceil_div(ceil_div(std::max<uint64_t>(max_out, 1), (uint64_t)kRouteThreads), (uint64_t)kScanRows);
-    const uint32_t zero_n = (buckets && rh.on && col_self()) ? (uint32_t)std::min<uint64_t>(nch_max, kSelfScanChunks) * rh.bins : 0u;
+    const uint32_t zero_n = (buckets && rh.on) ?(uint32_t)std::min<uint64_t>(nch_max, kSelfScanChunks) * rh.bins : 0u;
     uint32_t* zero_p = zero_n ? s.col_sums : nullptr;
     if (small) {
         hipLaunchKernelGGL((k_scan_reduce<1, kScanSmallChunk>), dim3(nbs), dim3(256), 0, st, poff32, (uint64_t)m, s.scan_sums,
@@ -5769,7 +5031,7 @@ int launch_bucket_acts(const uint32_t* d_act, size_t n, uint32_t n_act, uint32_t
                        void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return (int)hipMemsetAsync(d_offsets, 0, sizeof(uint32_t) * ((size_t)n_act + 2), st);
-    const RouteHist rh = route_hist(n_act, s);
+    const RouteHist rh = route_hist(n_act);
     const uint32_t ntiles = ceil_div(n, kTile);
     const bool pick = rh.on && hot_path_on(n, n_act, s);
     const bool hot = pick && hot_known(s);

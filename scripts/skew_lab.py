@@ -5,7 +5,7 @@ Until round 4 the level-2 launch form followed a host hint from the previous pla
 one had its hot bucket counted by ONE workgroup.  Since round 5 that stale case takes the fused kernel's chunked
 look-back form (same launch).  This lab times each batch of a sequence of uniform, Zipf and one-key-heavy batches with HIP
 events on the submission stream (no sync between batches), so the stale-hint batches show their cost next to the steady
-ones.  Run it once per ORL_SEG_FUSED setting (0: the round-3 count + scan launches for every plan):
+ones:
 
     python scripts/skew_lab.py [n_act] [n_msgs] [reps]
 """
@@ -64,8 +64,7 @@ def main():
             s.synchronize()
             for i, (name, e0, e1) in enumerate(evs):
                 times.setdefault(f"{i}:{name}", []).append(e0.elapsed_time(e1))
-    mode = "fused (device-decided skew form)" if os.environ.get("ORL_SEG_FUSED", "1") != "0" else "legacy (count + scan + carry)"
-    print(f"stage 4 alone, n_act {n_act}, {n} messages per batch, {mode}; median of {reps} sequences, ms per batch:")
+    print(f"stage 4 alone, n_act {n_act}, {n} messages per batch; median of {reps} sequences, ms per batch:")
     for k, v in times.items():
         print(f"  {k:>22}: {np.median(v):.3f}  (min {np.min(v):.3f})")
     eng.close()

@@ -1,5 +1,5 @@
 // stage4_ceiling.hip — the memory-pattern floors of stage 4's two-level counting sort at config 2 (64M messages, 1M
-// activations = 20-bit keys, 10 + 10 bits), against which k_radix_pass / k_seg_count / k_seg_scatter are judged.
+// activations = 20-bit keys, 10 + 10 bits), against which k_radix_pass / k_seg_count_scan / k_seg_scatter are judged.
 // Every floor moves the bytes of its kernel in the kernel's own global access pattern, with no ranking at all: the input
 // is laid out so each element's rank is known from its position (tiles and segments already in digit order, four
 // elements per digit, as a uniform 4096-element tile has on average), so what remains is the streaming read, the

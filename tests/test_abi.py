@@ -138,3 +138,28 @@ def test_registration_capacity_and_validation():
         eng.register_single_activation(keys, np.arange(20, dtype=np.uint32) % 8, np.zeros(20, np.uint8))
     assert e.value.code == L.E_CAPACITY
     eng.close()
+
+
+# the stage-4 A/B switches removed with their code, spelled without the prefix so that a grep of the tree
+# for one of them finds only the documents that record it
+REMOVED_SWITCHES = {"ORL_" + s for s in ("LSD_SWEEP", "STAGE4_SOA", "OFFSETS_SUFMIN", "SEG_FUSED", "LSD_FUSED_OFFSETS",
+                                         "BOUND_STAGED", "DIG8_WAVE", "LSD_DIGITS", "LSD_TILE12", "COL_SELF")}
+
+
+def test_env_switches_match_integration_doc():
+    """The environment switches the library reads (getenv("ORL_...") under orleans_amd/csrc) are exactly the ones
+    INTEGRATION.md documents in its "Directory memory and knobs" and fault-injection paragraphs, and none of the
+    stage-4 A/B switches whose code was removed is left in either.  Text files only."""
+    csrc = os.path.join(ROOT, "orleans_amd", "csrc")
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        read |= set(re.findall(r'getenv\("(ORL_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
+    paras = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("\n\n")
+    knobs = [p for p in paras if p.startswith("**Directory memory and knobs.**")]
+    inject = [p for p in paras if "fault injection" in p and "ORL_NODE_INJECT" in p]
+    assert len(knobs) == 1 and len(inject) == 1
+    header = open(os.path.join(ROOT, "include", "orleans_route.h")).read()
+    abi = set(re.findall(r"\bORL_[A-Z0-9_]+", re.sub(r"/\*.*?\*/|//[^\n]*", "", header, flags=re.S)))
+    documented = set(re.findall(r"`(ORL_[A-Z0-9_]+)(?:=[^`]*)?`", knobs[0] + inject[0])) - abi  # not the ABI's constants
+    assert read == documented, read ^ documented
+    assert not REMOVED_SWITCHES & (read | documented)

@@ -921,7 +921,7 @@ def test_lsd_offsets_long_gaps_vs_oracle(torch, monkeypatch, cap):
 @pytest.mark.parametrize("lsd_hot", ["0", "1"])
 def test_lsd_fused_offsets_dense_vs_oracle(torch, monkeypatch, lsd_hot):
     """The LSD plan's last pass writing the bucket offsets itself (round 6: OUT_FINAL_GAPS + k_bound_last / k_bound_scan /
-    k_bound_apply + k_sweep_tail), taken when a batch has >= 2 messages per bucket (config 3's shape; sparser batches keep
+    k_bound_apply + k_offsets_tail), taken when a batch has >= 2 messages per bucket (config 3's shape; sparser batches keep
     k_offsets_gaps).  n_act 8.5M (24-bit keys: 8 + 8 + 8-bit digits), batches of 18-20M messages: uniform, Zipf-hot (one key
     with millions of messages), a few keys with millions of empty buckets between and around them, the unresolved bucket,
     keys only in the low half, and the digit stream (OUT_PAIR_DIG) feeding each later histogram.  Order and offsets == the
@@ -970,15 +970,16 @@ def test_lsd_fused_offsets_dense_vs_oracle(torch, monkeypatch, lsd_hot):
 
 
 @pytest.mark.parametrize("n_act", [12_000_000, 40_000_000])
-def test_lsd_sweep_async_vs_oracle(torch, monkeypatch, n_act):
-    """The LSD plan's single-sweep passes (round 6: k_digit_hist, one k_sweep per digit with a decoupled look-back, the
-    final pass writing the bucket offsets itself, k_sweep_tail).  A sequence of batches enqueued on ONE stream with no host
-    sync in between, so the look-back ring and its ticket words are reused launch after launch at every size: large and
+def test_lsd_async_graph_vs_oracle(torch, n_act):
+    """The LSD plan's stage 4 (a histogram of the first digit, k_radix_pass per digit with the digit-stream histograms and
+    column scans between, the bucket offsets from the sorted keys: every batch here has fewer than two messages per bucket;
+    test_lsd_fused_offsets_dense_vs_oracle has the dense form) as a sequence of batches enqueued on ONE stream with no host
+    sync in between, so the scratch buffers and the long-gap queue are reused launch after launch at every size: large and
     small, Zipf-hot (a digit with millions of messages), one activation, the unresolved bucket, sparse keys (long empty
-    gaps, digits with no message), one message.  Each batch bit-exact vs the oracle's stable bucketing
-    (ActivationData.EnqueueMessage FIFO, ActivationData.cs:483-514) and equal to the default k_hist_pairs form (the sweep
-    is opt-in, ORL_LSD_SWEEP=1: slower on MI355X); then the same stage 4 captured in a hipGraph and replayed (the launch base lives on the device,
-    so a replay needs no host state).  n_act 12M: 8 + 8 + 8-bit digits; 40M: 9 + 9 + 8."""
+    gaps, digits with no message), one message.  Each batch bit-exact vs the oracle's stable bucketing (ActivationData.EnqueueMessage FIFO,
+    ActivationData.cs:483-514); then the same stage 4 captured in a hipGraph and replayed (the queue is emptied on the
+    device, so a replay needs no host state), and an eager batch after the replays.  n_act 12M: 8 + 8 + 8-bit digits;
+    40M: 9 + 9 + 8."""
     t = torch
     rng = np.random.default_rng(n_act + 1)
     o = cpu_ref.Oracle(8)
@@ -995,29 +996,22 @@ def test_lsd_sweep_async_vs_oracle(torch, monkeypatch, n_act):
                np.where(rng.random(1_000_000) < 0.4, np.uint32(L.NO_ACT), zipf(1_000_000)).astype(np.uint32),
                np.array([n_act - 1], np.uint32),
                zipf(2_000_000)]
-    monkeypatch.setenv("ORL_LSD_SWEEP", "1")  # opt-in (slower on MI355X: DESIGN §4)
     eng = GrainDirectoryEngine(n_act=n_act, dir_capacity=1024, max_batch=3_100_000, device=0)
-    monkeypatch.delenv("ORL_LSD_SWEEP")
     W.setup_engine(eng, W.default_cluster())
-    ref = GrainDirectoryEngine(n_act=n_act, dir_capacity=1024, max_batch=3_100_000, device=0)
-    W.setup_engine(ref, W.default_cluster())
     s = t.cuda.Stream()
     d_acts = [t.from_numpy(a.view(np.int32)).cuda() for a in batches]
-    outs, routs = [], []
+    outs = []
     with t.cuda.stream(s):
         for d_a in d_acts:
-            for e, acc in ((eng, outs), (ref, routs)):
-                order = t.full((len(d_a),), -1, dtype=t.int32, device="cuda")
-                off = t.full((n_act + 2,), -1, dtype=t.int32, device="cuda")
-                e.bucket_device(d_a, len(d_a), order, off, stream=s.cuda_stream)
-                acc.append((order, off))
+            order = t.full((len(d_a),), -1, dtype=t.int32, device="cuda")
+            off = t.full((n_act + 2,), -1, dtype=t.int32, device="cuda")
+            eng.bucket_device(d_a, len(d_a), order, off, stream=s.cuda_stream)
+            outs.append((order, off))
     s.synchronize()
     for k, a in enumerate(batches):
         eo, ef = o.bucket(a, n_act)
         np.testing.assert_array_equal(_u32(outs[k][1]), ef, err_msg=f"batch {k} offsets")
         np.testing.assert_array_equal(_u32(outs[k][0]), eo, err_msg=f"batch {k} order")
-        np.testing.assert_array_equal(_u32(routs[k][1]), ef, err_msg=f"batch {k} offsets (k_hist_pairs form)")
-        np.testing.assert_array_equal(_u32(routs[k][0]), eo, err_msg=f"batch {k} order (k_hist_pairs form)")
     assert eng.query(L.Q_STAGE4_ERROR) == 0
     # the Zipf batch captured once, replayed three times (zeroed outputs between), then an eager batch of another size
     order, off = outs[1]
@@ -1039,5 +1033,4 @@ def test_lsd_sweep_async_vs_oracle(torch, monkeypatch, n_act):
     np.testing.assert_array_equal(_u32(off2), ef, err_msg="eager after replays: offsets")
     np.testing.assert_array_equal(_u32(order2), eo, err_msg="eager after replays: order")
     assert eng.query(L.Q_STAGE4_ERROR) == 0
-    ref.close()
     eng.close()
