@@ -978,8 +978,8 @@ int orl_admit_device(orl_ctx* ctx, const uint32_t* d_act, const uint8_t* d_mflag
  * synchronise of `stream`, on this path only); if it is still over, ORL_E_CAPACITY, nothing launched, nothing changed.
  * Otherwise no call here synchronises or copies to the host.  A host-only context answers ORL_E_STATE; n or m above
  * max_batch ORL_E_CAPACITY; n == 0 and m == 0 are valid (m == 0 leaves an empty out list).  capacity < 2^32.
- * Left out: expiry of waiting messages, becameIdle and the activation collector, RunOnInactive, the host's forwarding of
- * drained messages, the queues inside orl_node_*. */
+ * Left out: expiry of waiting messages, RunOnInactive, the host's forwarding of drained messages, the queues inside
+ * orl_node_*.  becameIdle and the activation collector are orl_collector's, below. */
 #define ORL_TOK_NONE 0xFFFFFFFFu
 #define ORL_TOK_DRAIN 0xFFFFFFFEu
 #define ORL_WQ_RUN 0u
@@ -1006,6 +1006,124 @@ int orl_waitq_append_device(orl_ctx* ctx, orl_waitq* q, const uint32_t* d_tok, c
 int orl_complete_device(orl_ctx* ctx, orl_waitq* q, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
                         const uint32_t* d_corder, const uint32_t* d_cbucket_offsets, orl_act_state* d_state,
                         uint64_t* d_counts, void* stream);
+
+/* ---- the idle-activation collector: tickets, idleness, ScanStale / ScanAll ---------------------------------
+ * The last reader that would pull the state table back to the host: ActivationCollector (ActivationCollector.cs), driven
+ * by Catalog.CollectActivationsImpl (Catalog.cs:235-256).  It reads numRunning, waiting.Count and State of every
+ * activation it looks at, ResetRunning writes becameIdle (ActivationData.cs:427-435), and the collection ticket moves on
+ * every message arrival (Catalog.GetOrCreateActivation, Catalog.cs:427) and on every ResetRunning that reaches zero.
+ * The rule is admission's: the reference called in batch order.  Time is the caller's `now` in .NET ticks (> 0, not
+ * decreasing from call to call, now + an age limit < 2^63); nothing here reads a clock.
+ *
+ * orl_collector (opaque; one per context, for the context's n_act <= 2^31; one device allocation, zero-filled) holds
+ *   ticket[a]            i64  CollectionTicket; 0 = default(DateTime) = none
+ *   became_idle[a]       i64  becameIdle
+ *   keep_alive_until[a]  i64  DelayDeactivation's keepAliveUntil; INT64_MAX = DateTime.MaxValue, INT64_MIN or 0 = none;
+ *                             ShouldBeKeptAlive is keep_alive_until >= now (ActivationData.cs:642)
+ *   age_limit[a]         i64  CollectionAgeLimit; 0 = not initialised or disabled (ActivationCollector.cs:112-117)
+ *   cflags[a]            u8   ORL_COLF_EXEMPT (IsExemptFromCollection), ORL_COLF_CANCELLED (collectionCancelledFlag,
+ *                             ActivationData.cs:356-374)
+ *   quantum, next_ticket      host-side: the quantum given at create, nextTicket = MakeTicketFromDateTime(now0)
+ *   the condemned list        of the last scan: out_act[n_act] and a device u64 length; collector-owned and n_act long, so
+ *                             it cannot overflow; ASCENDING HANDLE order (the reference's order inside a bucket is a
+ *                             ConcurrentDictionary's, i.e. unspecified).
+ * orl_collector_view_get gives the device pointers (they never change) and the two host-side values.  The host writes
+ * age_limit, keep_alive_until, cflags and an initial became_idle through the view, as it writes running_tok above.
+ * The reference's buckets are not stored: ticket[a] and the cancelled bit carry everything it reads from them, because
+ * next_ticket only grows.
+ *
+ * mk(t) = ((t - 1) / quantum + 1) * quantum (MakeTicketFromDateTime :391-400).  A timeout below the quantum makes
+ * MakeTicketFromTimeSpan throw (:402-410); here the entry is left unchanged and counted as a bad timeout.
+ * expired(ticket) = ticket < next_ticket (:386-389).
+ *   schedule(a)    ScheduleCollection :103-128.  Exempt: nothing.  age_limit == 0: nothing.  age_limit < quantum: bad
+ *                  timeout.  ticket != 0: unchanged and counted (the reference throws).  Else ticket = mk(now + age_limit)
+ *                  and CANCELLED is cleared (Add :412-424).
+ *   reschedule(a)  TryRescheduleCollection :148-184.  Exempt: nothing.  ticket == 0: nothing.  Expired: ticket = 0.
+ *                  age_limit < quantum: bad timeout.  new = mk(now + age_limit): new == ticket nothing (the cancelled flag
+ *                  stays, :171); a CANCELLED entry gets ticket = 0 (Bucket.TryRemove fails :457-474, then
+ *                  ResetCollectionTicket :156); else ticket = new.  Idempotent for one `now`, so a batch applies it once
+ *                  per activation.
+ *   cancel(a)      TryCancelCollection :130-146.  Not exempt, ticket != 0 and not expired, not CANCELLED: CANCELLED is
+ *                  set, the ticket stays.
+ *
+ * Every call below is stream-ordered, launches nothing that waits on another workgroup and copies nothing to the host.
+ * d_counts (optional, device u64[8]) is zeroed on the stream and then receives the call's counts, in the order given.
+ *
+ * orl_collect_schedule_device / orl_collect_cancel_device apply schedule / cancel to m DISTINCT handles, one lane per
+ *   record; handles >= n_act are ignored and counted.  Call sites: Catalog.cs:507 (after InvokeActivate), :346, :804, :853.
+ *   counts, schedule: scheduled, exempt, age limit 0, bad timeout, already ticketed, handles >= n_act, 0, 0.
+ *   counts, cancel:   cancelled, exempt, no ticket, expired ticket, already cancelled, handles >= n_act, 0, 0.
+ *
+ * orl_collect_touch_device runs after orl_admit_device on the same stream (before or after orl_waitq_append_device) and
+ *   reads that call's d_act / d_disp in message order and the state table as admission left it.  It applies reschedule
+ *   once to every activation that at least one message of the batch took to Catalog.GetOrCreateActivation
+ *   (Dispatcher.cs:108) with an existing ActivationData: ORL_ADM_RUN, ENQUEUE, RESPONSE and INVALID always count;
+ *   EXPIRED, NONEXISTENT and UNRESOLVED never; OVERLOADED is rule 1 (IncomingMessageAgent, before the dispatcher: no
+ *   touch) or rule 7 (EnqueueRequest, after the lookup: a touch).  An activation whose only candidates are OVERLOADED was
+ *   rule 1 iff, after admission, state == VALID && L > 0 && in_flight + waiting > L (DESIGN §18 has the argument).
+ *   counts: activations touched, tickets moved, same ticket, expired ticket dropped, cancelled ticket dropped, bad
+ *   timeout, rule-1-only activations (not touched), rule-7-only activations (touched).
+ *
+ * orl_collect_on_complete_device is called BEFORE orl_complete_device on the same stream, with the same records and the
+ *   table as it is before completion.  For an activation with k >= 1 ordinary-token records and k >= num_running:
+ *   became_idle = now and reschedule (ActivationData.cs:427-435).  This is orl_complete_device's "apply all completions,
+ *   then pump once": where the per-completion order would pump a waiting request in before numRunning reads 0, this form
+ *   reschedules once more, which only ever makes the ticket of a busy activation later.
+ *   counts: activations that became idle, tickets moved, same ticket, expired ticket dropped, cancelled ticket dropped,
+ *   bad timeout, records with a handle >= n_act, ordinary-token records.
+ *
+ * orl_collect_scan_stale_device is ScanStale (:226-284).  The host advances next_ticket while next_ticket <= now
+ *   (DequeueQuantum :186-210); one dense scan over ticket[] (8 B per activation) takes every entry with ticket != 0 &&
+ *   ticket < next_ticket && !CANCELLED (CancelAll skips cancelled items, :476-494).  Per candidate: CANCELLED is set
+ *   (CancelAll) and ticket = 0, then
+ *     state != VALID                      nothing (bad state)
+ *     keep_alive_until >= now             schedule (kept alive)
+ *     num_running > 0 || waiting > 0      schedule (active)
+ *     now - became_idle < age_limit[a]    schedule (not stale)
+ *     otherwise                           d_state[a].state = ORL_ACT_DEACTIVATING (PrepareForDeactivation,
+ *                                         ActivationData.cs:337-341) and the handle joins the condemned list.
+ *   When nothing is dequeued the list is empty, its length is still written and nothing else is.
+ *   counts: candidates, bad state, kept alive, active, not stale, condemned, cancelled items skipped, deferred candidates
+ *   that schedule left without a ticket.
+ *
+ * orl_collect_scan_all_device is ScanAll(age_limit) (:291-345).  A candidate has ticket != 0 && !CANCELLED; it is
+ *   condemned iff state == VALID && keep_alive_until < now && num_running == 0 && waiting == 0 && now - became_idle >=
+ *   age_limit.  Then CANCELLED is set, the ticket stays (Bucket.TryCancel), state becomes DEACTIVATING and the handle
+ *   joins the list.  Cancelled entries are skipped: the reference finds a nulled item there and would take lock(null).
+ *   counts: as ScanStale's first seven; the eighth is 0.
+ *
+ * A host-only context answers ORL_E_STATE; m or n above max_batch ORL_E_CAPACITY; now <= 0 ORL_E_INVALID; m == 0 and
+ * n == 0 are valid. */
+#define ORL_COLF_EXEMPT 0x01u
+#define ORL_COLF_CANCELLED 0x02u
+typedef struct orl_collector orl_collector;
+typedef struct orl_collector_view {
+    int64_t* d_ticket;
+    int64_t* d_became_idle;
+    int64_t* d_keep_alive_until;
+    int64_t* d_age_limit;
+    uint8_t* d_cflags;
+    const uint32_t* d_out_act;
+    const uint64_t* d_out_n;
+    int64_t quantum;
+    int64_t next_ticket; /* as of this call */
+} orl_collector_view;
+int orl_collector_create(orl_ctx* ctx, int64_t quantum, int64_t now0, orl_collector** out);
+int orl_collector_destroy(orl_ctx* ctx, orl_collector* col);
+int orl_collector_view_get(orl_ctx* ctx, orl_collector* col, orl_collector_view* out);
+int orl_collect_schedule_device(orl_ctx* ctx, orl_collector* col, const uint32_t* d_handles, size_t m, int64_t now,
+                                uint64_t* d_counts, void* stream);
+int orl_collect_cancel_device(orl_ctx* ctx, orl_collector* col, const uint32_t* d_handles, size_t m, uint64_t* d_counts,
+                              void* stream);
+int orl_collect_touch_device(orl_ctx* ctx, orl_collector* col, const uint32_t* d_act, const uint8_t* d_disp, size_t n,
+                             const orl_act_state* d_state, const orl_admit_limits* limits, int64_t now, uint64_t* d_counts,
+                             void* stream);
+int orl_collect_on_complete_device(orl_ctx* ctx, orl_collector* col, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
+                                   const orl_act_state* d_state, int64_t now, uint64_t* d_counts, void* stream);
+int orl_collect_scan_stale_device(orl_ctx* ctx, orl_collector* col, orl_act_state* d_state, int64_t now, uint64_t* d_counts,
+                                  void* stream);
+int orl_collect_scan_all_device(orl_ctx* ctx, orl_collector* col, orl_act_state* d_state, int64_t age_limit, int64_t now,
+                                uint64_t* d_counts, void* stream);
 
 /* ---- device memory for callers without a GPU runtime (the P/Invoke silo) ---------------------------------
  * A .NET host drives the *_device entry points through these: allocate HBM on the context's device, copy host arrays

@@ -80,6 +80,15 @@ TOK_NONE, TOK_DRAIN = 0xFFFFFFFF, 0xFFFFFFFE
 WQ_RUN, WQ_DRAINED = 0, 1
 (CMP_COMPLETIONS, CMP_PUMPS, CMP_DRAINS, CMP_IGNORED, CMP_UNDERFLOWS, CMP_RUN, CMP_DRAINED,
  CMP_WAITING) = range(8)
+# orl_collector: cflags bits; the d_counts order of reschedule's outcomes (touch, on-complete) and of the two scans
+COLF_EXEMPT, COLF_CANCELLED = 0x01, 0x02
+COL_MOVED, COL_SAME, COL_EXPIRED, COL_CANCELLED_DROPPED, COL_BAD_TIMEOUT = 1, 2, 3, 4, 5
+COL_TOUCHED, COL_RULE1_ONLY, COL_RULE7_ONLY = 0, 6, 7
+COL_BECAME_IDLE, COL_IGNORED, COL_COMPLETIONS = 0, 6, 7
+(SCAN_CANDIDATES, SCAN_BAD_STATE, SCAN_KEPT_ALIVE, SCAN_ACTIVE, SCAN_NOT_STALE, SCAN_CONDEMNED, SCAN_CANCELLED_SKIPPED,
+ SCAN_UNSCHEDULED) = range(8)
+(SCHED_DONE, SCHED_EXEMPT, SCHED_AGE_ZERO, SCHED_BAD_TIMEOUT, SCHED_TICKETED, SCHED_IGNORED) = range(6)
+(CANCEL_DONE, CANCEL_EXEMPT, CANCEL_NO_TICKET, CANCEL_EXPIRED, CANCEL_ALREADY, CANCEL_IGNORED) = range(6)
 
 Q_PROBE_FORM, Q_FULL_UPLOADS, Q_SLOT_PATCHES, Q_DEVICE, Q_N_ACT, Q_MAX_BATCH, Q_RANK_MODE = 1, 2, 3, 4, 5, 6, 7
 Q_WIRE_DIGEST = 8
@@ -159,6 +168,12 @@ class orl_waitq_view(C.Structure):
                 ("d_running_tok", C.c_void_p), ("d_out_tok", C.c_void_p), ("d_out_act", C.c_void_p),
                 ("d_out_mflags", C.c_void_p), ("d_out_kind", C.c_void_p), ("d_out_n", C.c_void_p),
                 ("d_waiting_n", C.c_void_p)]
+
+
+class orl_collector_view(C.Structure):
+    _fields_ = [("d_ticket", C.c_void_p), ("d_became_idle", C.c_void_p), ("d_keep_alive_until", C.c_void_p),
+                ("d_age_limit", C.c_void_p), ("d_cflags", C.c_void_p), ("d_out_act", C.c_void_p), ("d_out_n", C.c_void_p),
+                ("quantum", C.c_int64), ("next_ticket", C.c_int64)]
 
 
 class orl_node_chunk_plan(C.Structure):
@@ -279,6 +294,15 @@ _SIGS = {
     "orl_waitq_view_get": (C.c_int, [_P, _P, C.POINTER(orl_waitq_view)]),
     "orl_waitq_append_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
     "orl_complete_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "orl_collector_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(_P)]),
+    "orl_collector_destroy": (C.c_int, [_P, _P]),
+    "orl_collector_view_get": (C.c_int, [_P, _P, C.POINTER(orl_collector_view)]),
+    "orl_collect_schedule_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int64, _P, _P]),
+    "orl_collect_cancel_device": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "orl_collect_touch_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.POINTER(orl_admit_limits), C.c_int64, _P, _P]),
+    "orl_collect_on_complete_device": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_int64, _P, _P]),
+    "orl_collect_scan_stale_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "orl_collect_scan_all_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]),
     "orl_ctx_set_rank_mode": (C.c_int, [_P, C.c_uint32]),
     "orl_device_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "orl_device_free": (C.c_int, [_P, _P]),

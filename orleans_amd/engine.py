@@ -21,6 +21,13 @@ lookup_many(_device)           RemoteGrainDirectory.LookUpMany (RemoteGrainDirec
 waitq_append_device            ActivationData.EnqueueMessage / RecordRunning (ActivationData.cs:487-514, 411-422)
 complete_device                ActivationData.ResetRunning (:424-442) + Dispatcher.RunMessagePump
                                (Dispatcher.cs:633-685)
+collect_schedule_device        ActivationCollector.ScheduleCollection (ActivationCollector.cs:103-128)
+collect_cancel_device          ActivationCollector.TryCancelCollection (:130-146)
+collect_touch_device           Catalog.GetOrCreateActivation's TryRescheduleCollection (Catalog.cs:427,
+                               ActivationCollector.cs:148-184)
+collect_on_complete_device     ActivationData.ResetRunning's idle branch (ActivationData.cs:427-435)
+collect_scan_stale_device      ActivationCollector.ScanStale (:226-284) with DequeueQuantum (:186-210)
+collect_scan_all_device        ActivationCollector.ScanAll (:291-345)
 =============================  ==================================================================
 
 Error behaviour: API errors raise ``OrleansRouteError`` (the reference throws ArgumentException /
@@ -903,6 +910,62 @@ class GrainDirectoryEngine:
         place.  d_counts: 8 uint64 (written; the CMP_* order)."""
         self._ck(self._lib.orl_complete_device(self._ctx, q, ptr(d_cact), ptr(d_ctok), int(m), ptr(d_corder),
                                                ptr(d_coffsets), ptr(d_state), ptr(d_counts), ptr(stream)))
+
+    def collector_create(self, quantum: int, now0: int) -> C.c_void_p:
+        """An idle-activation collector for this context's n_act (ActivationCollector's constructor): quantum in ticks,
+        next_ticket = MakeTicketFromDateTime(now0).  All per-activation arrays start at zero."""
+        col = C.c_void_p()
+        self._ck(self._lib.orl_collector_create(self._ctx, int(quantum), int(now0), C.byref(col)))
+        return col
+
+    def collector_destroy(self, col) -> None:
+        self._ck(self._lib.orl_collector_destroy(self._ctx, col))
+
+    def collector_view(self, col) -> "L.orl_collector_view":
+        """Device pointers of ticket, became_idle, keep_alive_until, age_limit (int64[n_act]), cflags (uint8[n_act]), the
+        condemned list of the last scan and its u64 length, and the host-side quantum and next_ticket."""
+        v = L.orl_collector_view()
+        self._ck(self._lib.orl_collector_view_get(self._ctx, col, C.byref(v)))
+        return v
+
+    def collect_schedule_device(self, col, d_handles, m: int, now: int, d_counts=None, stream=None) -> None:
+        """ActivationCollector.ScheduleCollection (ActivationCollector.cs:103-128) for m distinct handles, as
+        Catalog.cs:507 calls it after InvokeActivate.  d_counts: 8 uint64 (written; the SCHED_* order)."""
+        self._ck(self._lib.orl_collect_schedule_device(self._ctx, col, ptr(d_handles), int(m), int(now), ptr(d_counts),
+                                                       ptr(stream)))
+
+    def collect_cancel_device(self, col, d_handles, m: int, d_counts=None, stream=None) -> None:
+        """ActivationCollector.TryCancelCollection (:130-146) for m distinct handles (Catalog.cs:346, :804, :853).
+        d_counts: 8 uint64 (written; the CANCEL_* order)."""
+        self._ck(self._lib.orl_collect_cancel_device(self._ctx, col, ptr(d_handles), int(m), ptr(d_counts), ptr(stream)))
+
+    def collect_touch_device(self, col, d_act, d_disp, n: int, d_state, now: int, hard: int = 0, hard_stateless: int = 0,
+                             d_counts=None, stream=None) -> None:
+        """After admit_device on the same stream: TryRescheduleCollection (:148-184) once for every activation a message
+        of the batch reached through Catalog.GetOrCreateActivation (Catalog.cs:427).  d_act / d_disp in message order,
+        d_state and the limits as admission had them.  d_counts: 8 uint64 (written; COL_TOUCHED, COL_MOVED .. COL_BAD_TIMEOUT,
+        COL_RULE1_ONLY, COL_RULE7_ONLY)."""
+        lim = L.orl_admit_limits(int(hard), int(hard_stateless))
+        self._ck(self._lib.orl_collect_touch_device(self._ctx, col, ptr(d_act), ptr(d_disp), int(n), ptr(d_state),
+                                                    C.byref(lim), int(now), ptr(d_counts), ptr(stream)))
+
+    def collect_on_complete_device(self, col, d_cact, d_ctok, m: int, d_state, now: int, d_counts=None, stream=None) -> None:
+        """Before complete_device on the same stream, with the same records: an activation whose completions take
+        numRunning to 0 gets becameIdle = now and TryRescheduleCollection (ActivationData.cs:427-435).  d_counts: 8 uint64
+        (written; COL_BECAME_IDLE, COL_MOVED .. COL_BAD_TIMEOUT, COL_IGNORED, COL_COMPLETIONS)."""
+        self._ck(self._lib.orl_collect_on_complete_device(self._ctx, col, ptr(d_cact), ptr(d_ctok), int(m), ptr(d_state),
+                                                          int(now), ptr(d_counts), ptr(stream)))
+
+    def collect_scan_stale_device(self, col, d_state, now: int, d_counts=None, stream=None) -> None:
+        """ActivationCollector.ScanStale (:226-284): dequeues every quantum up to `now`; the condemned activations become
+        ACT_DEACTIVATING in d_state and their handles, ascending, are the collector's list (collector_view).  d_counts: 8
+        uint64 (written; the SCAN_* order)."""
+        self._ck(self._lib.orl_collect_scan_stale_device(self._ctx, col, ptr(d_state), int(now), ptr(d_counts), ptr(stream)))
+
+    def collect_scan_all_device(self, col, d_state, age_limit: int, now: int, d_counts=None, stream=None) -> None:
+        """ActivationCollector.ScanAll(ageLimit) (:291-345); results as collect_scan_stale_device."""
+        self._ck(self._lib.orl_collect_scan_all_device(self._ctx, col, ptr(d_state), int(age_limit), int(now), ptr(d_counts),
+                                                       ptr(stream)))
 
     def copy_to_host(self, h_dst: np.ndarray, d_src, nbytes: Optional[int] = None, stream=None) -> np.ndarray:
         """orl_copy_to_host + orl_stream_sync (the P/Invoke caller's way to read device outputs)."""
