@@ -6,6 +6,8 @@ SRC = orleans_amd/csrc/route_kernels.hip orleans_amd/csrc/dir_mutate.hip orleans
 HDR = include/orleans_route.h orleans_amd/csrc/orl_internal.h orleans_amd/csrc/part_lb_body.inc
 # device-side table helpers, included by the .hip files only
 DEVHDR = orleans_amd/csrc/dir_table_dev.h
+# device-side scan helpers of the scan-shaped .hip files
+SCANHDR = orleans_amd/csrc/tile_scan_dev.h
 LIB = orleans_amd/liborleans_route.so
 OBJ = build/route_kernels.o build/dir_mutate.o build/cache_evict.o build/cache_adaptive.o build/dir_versions.o build/admit.o build/waitq.o build/collect.o build/wire_codec.o build/orl_api.o build/orl_node.o
 # RCCL (the node exchange); inside a torch process the soname resolves to torch's loaded copy
@@ -24,11 +26,11 @@ build/dir_mutate.o: orleans_amd/csrc/dir_mutate.hip $(DEVHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/cache_evict.o: orleans_amd/csrc/cache_evict.hip orleans_amd/csrc/cache_evict.h orleans_amd/csrc/cache_adaptive.h $(DEVHDR) $(HDR)
+build/cache_evict.o: orleans_amd/csrc/cache_evict.hip orleans_amd/csrc/cache_evict.h orleans_amd/csrc/cache_adaptive.h $(DEVHDR) $(SCANHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/cache_adaptive.o: orleans_amd/csrc/cache_adaptive.hip orleans_amd/csrc/cache_adaptive.h $(DEVHDR) $(HDR)
+build/cache_adaptive.o: orleans_amd/csrc/cache_adaptive.hip orleans_amd/csrc/cache_adaptive.h $(DEVHDR) $(SCANHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
@@ -36,15 +38,15 @@ build/dir_versions.o: orleans_amd/csrc/dir_versions.hip orleans_amd/csrc/dir_ver
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/admit.o: orleans_amd/csrc/admit.hip orleans_amd/csrc/admit.h $(HDR)
+build/admit.o: orleans_amd/csrc/admit.hip orleans_amd/csrc/admit.h $(SCANHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/waitq.o: orleans_amd/csrc/waitq.hip orleans_amd/csrc/waitq.h $(HDR)
+build/waitq.o: orleans_amd/csrc/waitq.hip orleans_amd/csrc/waitq.h $(SCANHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
-build/collect.o: orleans_amd/csrc/collect.hip orleans_amd/csrc/collect.h $(HDR)
+build/collect.o: orleans_amd/csrc/collect.hip orleans_amd/csrc/collect.h $(SCANHDR) $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

@@ -6,15 +6,6 @@
 
 namespace orl {
 
-constexpr uint32_t kAdmitThreads = 256;
-constexpr uint32_t kAdmitItems = 8;
-constexpr uint32_t kAdmitTile = kAdmitThreads * kAdmitItems;  // positions of `order` per workgroup
-
-// A segment-scan value (admit.hip gives the two scans their meaning); one per tile in AdmitScratch.
-struct AdmitSeg {
-    uint32_t a, b, f, pad;
-};
-
 // Scratch of one context's admission calls, allocated once (on the first call), sized by max_batch: one device
 // allocation (`base`) carved into the arrays below.  The per-position arrays are padded to whole tiles.
 struct AdmitScratch {
@@ -22,8 +13,8 @@ struct AdmitScratch {
     uint64_t cap = 0;          // positions (max_batch)
     uint32_t* key = nullptr;   // [cap, padded] min(act[order[p]], n_act)
     uint8_t* cls = nullptr;    // [cap, padded] the message's class, then its provisional disposition
-    AdmitSeg* agg1 = nullptr;  // [tiles] per-tile aggregates of the first scan, then their exclusive scan
-    AdmitSeg* agg2 = nullptr;  // [tiles] the same of the second scan
+    SegAgg* agg1 = nullptr;    // [tiles] per-tile aggregates of the first scan, then their exclusive scan
+    SegAgg* agg2 = nullptr;    // [tiles] the same of the second scan
 };
 
 // hipError_t as int (0 = ok).

@@ -36,13 +36,13 @@
 #include <hip/hip_runtime.h>
 
 #include "admit.h"
+#include "tile_scan_dev.h"
 
 namespace orl {
 
 namespace {
 
-constexpr uint32_t kT = kAdmitThreads, kI = kAdmitItems;
-constexpr uint32_t kScanThreads = 1024;  // k_adm_tilescan's one workgroup
+constexpr uint32_t kT = kTileThreads, kI = kTileItems;
 
 // cls[p] as k_adm_classify writes it
 constexpr uint32_t kClsReq = 0x01, kClsRo = 0x02, kClsAi = 0x04, kClsExp = 0x08, kClsResp = 0x10, kClsHead = 0x20;
@@ -50,10 +50,6 @@ constexpr uint32_t kClsReq = 0x01, kClsRo = 0x02, kClsAi = 0x04, kClsExp = 0x08,
 // (the bucket's first request is known at p, and read-only)
 constexpr uint32_t kDecCode = 0x07, kDecSat = 0x08, kDecHead = 0x10, kDecRo = 0x20, kDecKnown = 0x40;
 constexpr uint32_t kNoCode = 0xFF;
-
-struct Seg {
-    uint32_t a, b, f;
-};
 
 // Scan 1.  a = requests since the span's last bucket head, b = the first of them (0 none, 1 read-write, 2 read-only),
 // f = 1: the span holds a bucket head.
@@ -85,117 +81,19 @@ __device__ __forceinline__ Seg seg_adm(uint32_t dec) {
                ((dec & kDecHead) ? 1u : 0u) | ((dec & kDecSat) ? 2u : 0u)};
 }
 
-// Inclusive Hillis-Steele scan of one value per thread through LDS (2 * N values); returns the exclusive prefix of
-// thread t and the workgroup's total.  Ends on a barrier: `lds` may be reused at once.
-template <class Op, uint32_t N>
-__device__ __forceinline__ Seg block_exclusive(Seg mine, Seg* lds, Seg* total) {
-    const uint32_t t = threadIdx.x;
-    Seg* src = lds;
-    Seg* dst = lds + N;
-    src[t] = mine;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t d = 1; d < N; d <<= 1) {
-        Seg v = src[t];
-        if (t >= d) v = Op::op(src[t - d], v);
-        dst[t] = v;
-        __syncthreads();
-        Seg* sw = src;
-        src = dst;
-        dst = sw;
-    }
-    const Seg ex = t ? src[t - 1] : Seg{0, 0, 0};
-    *total = src[N - 1];
-    __syncthreads();
-    return ex;
-}
-
-// The 8 bytes / 8 words of thread t's positions in a tile-padded scratch array.
-__device__ __forceinline__ void load_bytes(const uint8_t* p, uint32_t (&v)[kI]) {
-    const uint2 w = *reinterpret_cast<const uint2*>(p);
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        v[k] = (w.x >> (8 * k)) & 0xFFu;
-        v[k + 4] = (w.y >> (8 * k)) & 0xFFu;
-    }
-}
-
-__device__ __forceinline__ void store_bytes(uint8_t* p, const uint32_t (&v)[kI]) {
-    uint2 w;
-    w.x = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-    w.y = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
-    *reinterpret_cast<uint2*>(p) = w;
-}
-
-__device__ __forceinline__ void load_words(const uint32_t* p, uint32_t (&v)[kI]) {
-    const uint4 lo = *reinterpret_cast<const uint4*>(p), hi = *reinterpret_cast<const uint4*>(p + 4);
-    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-    v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-}
-
-// order[p0 .. p0 + 8) of the caller's array, streamed (non-temporal); 0 past n.
-__device__ __forceinline__ void load_order(const uint32_t* __restrict__ order, size_t p0, size_t n, bool vec,
-                                           uint32_t (&v)[kI]) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    if (vec && p0 + kI <= n) {
-        const u32x4 lo = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(order + p0));
-        const u32x4 hi = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(order + p0 + 4));
-        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-        v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < kI; ++k) v[k] = p0 + k < n ? __builtin_nontemporal_load(order + p0 + k) : 0u;
-    }
-}
-
-// The bucket of position p: the smallest b in [lo, n_act] with off[b + 1] > p (off[n_act + 1] = n > p).  At most 32 steps.
-__device__ __forceinline__ uint32_t bucket_of(const uint32_t* __restrict__ off, uint32_t lo, uint32_t n_act, size_t p) {
-    uint32_t hi = n_act;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if ((size_t)off[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 // The key of a position comes from the offsets, not from act[order[p]]: a search per thread and one more per bucket
 // boundary inside its 8 positions (the next bucket first), against a random 4-byte gather per position.
 __global__ __launch_bounds__(kT) void k_adm_classify(const uint8_t* __restrict__ mflags, size_t n, uint32_t n_act,
                                                      const uint32_t* __restrict__ order, bool order_vec,
                                                      const uint32_t* __restrict__ off, uint32_t* __restrict__ key_out,
-                                                     uint8_t* __restrict__ cls_out, AdmitSeg* __restrict__ agg) {
+                                                     uint8_t* __restrict__ cls_out, SegAgg* __restrict__ agg) {
     __shared__ Seg lds[2 * kT];
-    const size_t p0 = (size_t)blockIdx.x * kAdmitTile + (size_t)threadIdx.x * kI;
+    const size_t p0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     uint32_t idx[kI], key[kI], cls[kI], head = 0;
     load_order(order, p0, n, order_vec, idx);
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) cls[k] = p0 + k < n ? mflags[idx[k]] : 0u;  // 8 gathers in flight together
-    uint32_t b = n_act;
-    size_t begin = 0, end = 0;  // bucket b = [begin, end)
-    if (p0 < n) {
-        b = bucket_of(off, 0, n_act, p0);
-        begin = off[b];
-        end = off[b + 1];
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kI; ++k) {
-        const size_t p = p0 + k;
-        if (p < n && p >= end && b < n_act) {  // the last bucket ends at n: b < n_act holds for stage 4's offsets
-            const size_t next_end = off[b + 2];
-            if (p < next_end) {
-                b += 1;
-                begin = end;
-                end = next_end;
-            } else {
-                b = bucket_of(off, b + 2 < n_act ? b + 2 : n_act, n_act, p);
-                begin = off[b];
-                end = off[b + 1];
-            }
-        }
-        key[k] = p < n ? b : n_act;
-        head |= (p < n && p == begin ? 1u : 0u) << k;
-    }
+    bucket_keys(off, n_act, p0, n, key, &head);
     Seg sum{0, 0, 0};
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -213,37 +111,23 @@ __global__ __launch_bounds__(kT) void k_adm_classify(const uint8_t* __restrict__
     ko[1] = make_uint4(key[4], key[5], key[6], key[7]);
     store_bytes(cls_out + p0, cls);
     Seg total;
-    (void)block_exclusive<OpReq, kT>(sum, lds, &total);
-    if (threadIdx.x == 0) agg[blockIdx.x] = AdmitSeg{total.a, total.b, total.f, 0};
+    (void)block_exclusive<Seg, OpReq, kT>(sum, lds, &total);
+    if (threadIdx.x == 0) agg[blockIdx.x] = SegAgg(total);
 }
 
-// In place: agg[i] = the fold of agg[0 .. i).  One workgroup; thread t owns the chunk [t * chunk, (t + 1) * chunk).
+// In place: agg[i] = the fold of agg[0 .. i) (tile_scan_body).
 template <class Op>
-__global__ __launch_bounds__(kScanThreads) void k_adm_tilescan(AdmitSeg* __restrict__ agg, uint32_t ntiles) {
+__global__ __launch_bounds__(kScanThreads) void k_adm_tilescan(SegAgg* __restrict__ agg, uint32_t ntiles) {
     __shared__ Seg lds[2 * kScanThreads];
-    const uint32_t chunk = (ntiles + kScanThreads - 1) / kScanThreads;
-    const uint32_t lo = threadIdx.x * chunk < ntiles ? threadIdx.x * chunk : ntiles;
-    const uint32_t hi = ntiles - lo < chunk ? ntiles : lo + chunk;
-    Seg sum{0, 0, 0};
-    for (uint32_t i = lo; i < hi; ++i) {
-        const AdmitSeg v = agg[i];
-        sum = Op::op(sum, Seg{v.a, v.b, v.f});
-    }
-    Seg total;
-    Seg run = block_exclusive<Op, kScanThreads>(sum, lds, &total);
-    for (uint32_t i = lo; i < hi; ++i) {
-        const AdmitSeg v = agg[i];
-        agg[i] = AdmitSeg{run.a, run.b, run.f, 0};
-        run = Op::op(run, Seg{v.a, v.b, v.f});
-    }
+    tile_scan_body<Seg, SegAgg, Op>(agg, ntiles, lds);
 }
 
 __global__ __launch_bounds__(kT) void k_adm_decide(uint32_t n_act, const orl_act_state* __restrict__ state,
                                                    orl_admit_limits lim, const uint32_t* __restrict__ key_in,
-                                                   uint8_t* __restrict__ cls_io, const AdmitSeg* __restrict__ carry1,
-                                                   AdmitSeg* __restrict__ agg2) {
+                                                   uint8_t* __restrict__ cls_io, const SegAgg* __restrict__ carry1,
+                                                   SegAgg* __restrict__ agg2) {
     __shared__ Seg lds[2 * kT];
-    const size_t p0 = (size_t)blockIdx.x * kAdmitTile + (size_t)threadIdx.x * kI;
+    const size_t p0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     uint32_t key[kI], cls[kI];
     load_words(key_in + p0, key);
     load_bytes(cls_io + p0, cls);
@@ -251,9 +135,9 @@ __global__ __launch_bounds__(kT) void k_adm_decide(uint32_t n_act, const orl_act
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) sum = OpReq::op(sum, seg_req(cls[k]));
     Seg total;
-    const Seg ex = block_exclusive<OpReq, kT>(sum, lds, &total);
-    const AdmitSeg cin = carry1[blockIdx.x];
-    Seg run = OpReq::op(Seg{cin.a, cin.b, cin.f}, ex);
+    const Seg ex = block_exclusive<Seg, OpReq, kT>(sum, lds, &total);
+    const SegAgg cin = carry1[blockIdx.x];
+    Seg run = OpReq::op(Seg(cin), ex);
     Seg sum2{0, 0, 0};
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -310,18 +194,18 @@ __global__ __launch_bounds__(kT) void k_adm_decide(uint32_t n_act, const orl_act
         sum2 = OpAdm::op(sum2, seg_adm(dec));
     }
     store_bytes(cls_io + p0, cls);
-    (void)block_exclusive<OpAdm, kT>(sum2, lds, &total);
-    if (threadIdx.x == 0) agg2[blockIdx.x] = AdmitSeg{total.a, total.b, total.f, 0};
+    (void)block_exclusive<Seg, OpAdm, kT>(sum2, lds, &total);
+    if (threadIdx.x == 0) agg2[blockIdx.x] = SegAgg(total);
 }
 
 __global__ __launch_bounds__(kT) void k_adm_resolve(size_t n, uint32_t n_act, const uint32_t* __restrict__ order,
                                                     bool order_vec, const uint32_t* __restrict__ key_in,
-                                                    const uint8_t* __restrict__ dec_in, const AdmitSeg* __restrict__ carry2,
+                                                    const uint8_t* __restrict__ dec_in, const SegAgg* __restrict__ carry2,
                                                     orl_act_state* __restrict__ state, uint8_t* __restrict__ disp,
                                                     uint64_t* __restrict__ counts) {
     __shared__ Seg lds[2 * kT];
     __shared__ uint32_t cnt_lds[8];
-    const size_t p0 = (size_t)blockIdx.x * kAdmitTile + (size_t)threadIdx.x * kI;
+    const size_t p0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     uint32_t idx[kI], dec[kI];
     load_order(order, p0, n, order_vec, idx);
     load_bytes(dec_in + p0, dec);
@@ -330,9 +214,9 @@ __global__ __launch_bounds__(kT) void k_adm_resolve(size_t n, uint32_t n_act, co
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) sum = OpAdm::op(sum, seg_adm(dec[k]));
     Seg total;
-    const Seg ex = block_exclusive<OpAdm, kT>(sum, lds, &total);
-    const AdmitSeg cin = carry2[blockIdx.x];
-    Seg run = OpAdm::op(Seg{cin.a, cin.b, cin.f}, ex);
+    const Seg ex = block_exclusive<Seg, OpAdm, kT>(sum, lds, &total);
+    const SegAgg cin = carry2[blockIdx.x];
+    Seg run = OpAdm::op(Seg(cin), ex);
     // the head bit of the position after this thread's last: the next thread's first, in the padded array
     const uint32_t next_dec = p0 + kI < n ? dec_in[p0 + kI] : 0u;
     uint32_t code[kI];
@@ -366,42 +250,25 @@ __global__ __launch_bounds__(kT) void k_adm_resolve(size_t n, uint32_t n_act, co
             }
         }
     }
-    if (counts) {  // uniform; every lane of the wave reaches the ballots
-        uint32_t wc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t k = 0; k < kI; ++k) {
-#pragma unroll
-            for (uint32_t q = 0; q < 8; ++q) wc[q] += (uint32_t)__popcll(__ballot(code[k] == q));
-        }
-        if ((threadIdx.x & 63u) == 0) {
-#pragma unroll
-            for (uint32_t q = 0; q < 8; ++q)
-                if (wc[q]) atomicAdd(&cnt_lds[q], wc[q]);
-        }
-        __syncthreads();
-        if (threadIdx.x < 8 && cnt_lds[threadIdx.x])
-            atomicAdd(reinterpret_cast<unsigned long long*>(counts + threadIdx.x), (unsigned long long)cnt_lds[threadIdx.x]);
-    }
+    if (counts) ballot_counts<8>(code, cnt_lds, counts);  // uniform; every lane of the wave reaches the ballots
 }
-
-uint64_t pad_tile(uint64_t v) { return (v + kAdmitTile - 1) / kAdmitTile * kAdmitTile; }
 
 }  // namespace
 
 int admit_alloc(AdmitScratch* s, uint64_t max_batch) {
     if (s->base) return 0;
-    const uint64_t cap = pad_tile(max_batch ? max_batch : 1), tiles = cap / kAdmitTile;
-    const uint64_t b_key = cap * sizeof(uint32_t), b_cls = pad_tile(cap), b_agg = tiles * sizeof(AdmitSeg);
+    const uint64_t cap = pad_to(max_batch ? max_batch : 1, kScanTile), tiles = cap / kScanTile;
+    const uint64_t b_key = cap * sizeof(uint32_t), b_cls = cap, b_agg = tiles * sizeof(SegAgg);
     void* base = nullptr;
     hipError_t e = hipMalloc(&base, b_key + b_cls + 2 * b_agg);
     if (e != hipSuccess) return (int)e;
-    uint8_t* p = static_cast<uint8_t*>(base);
+    Carve c(base);
     s->base = base;
     s->cap = max_batch;
-    s->key = reinterpret_cast<uint32_t*>(p);
-    s->cls = p + b_key;
-    s->agg1 = reinterpret_cast<AdmitSeg*>(p + b_key + b_cls);
-    s->agg2 = s->agg1 + tiles;
+    s->key = c.take<uint32_t>(b_key);
+    s->cls = c.take(b_cls);
+    s->agg1 = c.take<SegAgg>(b_agg);
+    s->agg2 = c.take<SegAgg>(b_agg);
     return 0;
 }
 
@@ -419,7 +286,7 @@ int launch_admit(const uint8_t* d_mflags, size_t n, uint32_t n_act, const uint32
         if (e != hipSuccess) return (int)e;
     }
     if (n == 0) return 0;
-    const uint32_t tiles = (uint32_t)((n + kAdmitTile - 1) / kAdmitTile);
+    const uint32_t tiles = (uint32_t)((n + kScanTile - 1) / kScanTile);
     const bool order_vec = ((uintptr_t)d_order & 15u) == 0;
     hipLaunchKernelGGL(k_adm_classify, dim3(tiles), dim3(kT), 0, st, d_mflags, n, n_act, d_order, order_vec, d_off,
                        s.key, s.cls, s.agg1);

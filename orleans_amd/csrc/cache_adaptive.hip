@@ -13,6 +13,7 @@
 
 #include "cache_adaptive.h"
 #include "dir_table_dev.h"
+#include "tile_scan_dev.h"
 
 namespace orl {
 
@@ -85,21 +86,14 @@ __global__ __launch_bounds__(256) void k_sw_classify(const RouteParams* __restri
 // by one workgroup, each thread a contiguous piece; owner_off[o] = the position where owner o's list begins.
 __global__ __launch_bounds__(256) void k_sw_scan(uint32_t* __restrict__ tile_cnt, uint32_t ntiles, uint32_t n_silos,
                                                  uint32_t* __restrict__ owner_off) {
-    __shared__ uint32_t lds[256];
+    __shared__ uint32_t lds[2 * 256];
     const uint32_t len = n_silos * ntiles;
     const uint32_t per = (len + 255u) / 256u;
     const uint32_t b = threadIdx.x * per < len ? threadIdx.x * per : len, e = b + per < len ? b + per : len;
     uint32_t sum = 0;
     for (uint32_t t = b; t < e; ++t) sum += tile_cnt[t];
-    lds[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const uint32_t add = threadIdx.x >= d ? lds[threadIdx.x - d] : 0u;
-        __syncthreads();
-        lds[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = lds[threadIdx.x] - sum;
+    uint32_t total;
+    uint32_t run = block_exclusive<uint32_t, OpAdd, 256>(sum, lds, &total);
     uint32_t next_owner = (b + ntiles - 1) / ntiles;  // the first owner whose list begins at or after b
     for (uint32_t t = b; t < e; ++t) {
         if (t == next_owner * ntiles) owner_off[next_owner++] = run;
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(256) void k_sw_scan(uint32_t* __restrict__ tile_cnt
         tile_cnt[t] = run;
         run += v;
     }
-    if (threadIdx.x == 255) owner_off[n_silos] = lds[255];
+    if (threadIdx.x == 255) owner_off[n_silos] = total;
 }
 
 // Pass 2: tombstones for the self-owned and the expired, and for every entry to refresh its (grain, ETag) at the

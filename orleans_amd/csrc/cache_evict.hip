@@ -15,6 +15,7 @@
 #include "cache_adaptive.h"
 #include "cache_evict.h"
 #include "dir_table_dev.h"
+#include "tile_scan_dev.h"
 
 namespace orl {
 
@@ -31,23 +32,6 @@ constexpr uint32_t kErrInvariant = 2u;
 enum { ST_NVALID = 0, ST_K = 1, ST_PREFIX = 2, ST_RANK = 3, ST_NCAND = 4, ST_FINAL = 5, ST_EVICTED = 6, ST_REBUILT = 7 };
 
 __device__ __forceinline__ void raise(uint64_t* cnt, uint32_t bit) { atomicOr(reinterpret_cast<uint32_t*>(cnt + 2), bit); }
-
-// Exclusive scan of one value per thread over a 256-thread block; *total gets the block's sum.
-__device__ __forceinline__ uint32_t block_scan_256(uint32_t v, uint32_t* lds /* [256] */, uint32_t* total) {
-    const uint32_t t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        const uint32_t add = t >= d ? lds[t - d] : 0u;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const uint32_t incl = lds[t];
-    *total = lds[255];
-    __syncthreads();
-    return incl - v;
-}
 
 // ---- preparation ---------------------------------------------------------------------------------------------------
 
@@ -205,13 +189,13 @@ __global__ __launch_bounds__(256) void k_ev_ccount(const uint64_t* __restrict__ 
 
 __global__ __launch_bounds__(256) void k_ev_cscan(uint32_t* __restrict__ tile_cnt, uint32_t ntiles, uint64_t* __restrict__ st,
                                                   uint32_t ncap, uint64_t* __restrict__ cnt) {
-    __shared__ uint32_t lds[256];
+    __shared__ uint32_t lds[2 * 256];
     const uint32_t per = (ntiles + 255u) / 256u;
     const uint32_t b = threadIdx.x * per, e = b + per < ntiles ? b + per : ntiles;
     uint32_t sum = 0;
     for (uint32_t t = b; t < e; ++t) sum += tile_cnt[t];
     uint32_t total;
-    uint32_t run = block_scan_256(sum, lds, &total);
+    uint32_t run = block_exclusive<uint32_t, OpAdd, 256>(sum, lds, &total);
     for (uint32_t t = b; t < e; ++t) {
         const uint32_t v = tile_cnt[t];
         tile_cnt[t] = run;
@@ -229,7 +213,7 @@ __global__ __launch_bounds__(256) void k_ev_cscan(uint32_t* __restrict__ tile_cn
 __global__ __launch_bounds__(256) void k_ev_cemit(const uint64_t* __restrict__ skey, uint64_t slots, const uint64_t* __restrict__ st,
                                                   const uint32_t* __restrict__ tile_off, uint64_t* __restrict__ cand_stamp,
                                                   uint32_t* __restrict__ cand_slot, uint32_t ncap) {
-    __shared__ uint32_t lds[256];
+    __shared__ uint32_t lds[2 * 256];
     const uint64_t K = st[ST_K], T = st[ST_PREFIX];
     const uint64_t s0 = (uint64_t)blockIdx.x * kEvTile + threadIdx.x * 8u;
     uint64_t v[8];
@@ -240,7 +224,7 @@ __global__ __launch_bounds__(256) void k_ev_cemit(const uint64_t* __restrict__ s
         c += (v[e] != ~0ull && v[e] <= T) ? 1u : 0u;
     }
     uint32_t total;
-    uint32_t pos = tile_off[blockIdx.x] + block_scan_256(c, lds, &total);
+    uint32_t pos = tile_off[blockIdx.x] + block_exclusive<uint32_t, OpAdd, 256>(c, lds, &total);
     for (uint32_t e = 0; e < 8; ++e)
         if (v[e] != ~0ull && v[e] <= T) {
             if (pos < ncap) {

@@ -4,14 +4,6 @@
 
 #include "orl_internal.h"
 
-namespace orl {
-
-constexpr uint32_t kColThreads = 256;
-constexpr uint32_t kColItems = 8;
-constexpr uint32_t kColTile = kColThreads * kColItems;  // activations / records per workgroup
-
-}  // namespace orl
-
 // One collector: the five per-activation arrays, the condemned list of the last scan and the scratch of its calls, all
 // carved from one device allocation (`base`), zero-filled.  Per-activation arrays are padded to whole tiles; a padding
 // entry keeps ticket == 0 and so is never a candidate of a scan.

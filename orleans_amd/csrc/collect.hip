@@ -25,13 +25,13 @@
 #include <hip/hip_runtime.h>
 
 #include "collect.h"
+#include "tile_scan_dev.h"
 
 namespace orl {
 
 namespace {
 
-constexpr uint32_t kT = kColThreads, kI = kColItems;
-constexpr uint32_t kScanThreads = 1024;  // k_col_tilescan's one workgroup
+constexpr uint32_t kT = kTileThreads, kI = kTileItems;
 
 constexpr uint32_t kMarkCertain = 0x1, kMarkOverloaded = 0x2;
 
@@ -47,22 +47,6 @@ Cols cols_of(const orl_collector& c) { return Cols{c.ticket, c.became_idle, c.ke
 
 // MakeTicketFromDateTime (ActivationCollector.cs:391-400): t rounded up to a multiple of the quantum; t > 0.
 __device__ __forceinline__ int64_t make_ticket(int64_t t, int64_t quantum) { return ((t - 1) / quantum + 1) * quantum; }
-
-// d_counts sums of one workgroup: lanes add to LDS, 8 lanes add the non-zero sums to the device array.
-struct BlockCounts {
-    uint32_t* lds;
-    __device__ __forceinline__ void init(uint32_t* p) {
-        lds = p;
-        if (threadIdx.x < 8) lds[threadIdx.x] = 0;
-        __syncthreads();
-    }
-    __device__ __forceinline__ void add(uint32_t q, uint32_t v = 1) { atomicAdd(&lds[q], v); }
-    __device__ __forceinline__ void flush(uint64_t* counts) {  // every thread of the workgroup calls it
-        __syncthreads();
-        if (counts && threadIdx.x < 8 && lds[threadIdx.x])
-            atomicAdd(reinterpret_cast<unsigned long long*>(counts + threadIdx.x), (unsigned long long)lds[threadIdx.x]);
-    }
-};
 
 // TryRescheduleCollection (ActivationCollector.cs:148-184) of entry a.  -> 0 nothing (exempt, or no ticket), else the
 // d_counts slot of what happened: 1 moved, 2 same ticket, 3 expired ticket dropped, 4 cancelled ticket dropped, 5 bad
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(kT) void k_col_cancel(Cols c, const uint32_t* __res
 // A set bit is not set again: the read may be stale, the OR is monotone.
 __global__ __launch_bounds__(kT) void k_col_touch_mark(const uint32_t* __restrict__ act, const uint8_t* __restrict__ disp,
                                                        size_t n, uint32_t n_act, uint32_t* __restrict__ mark) {
-    const size_t base = (size_t)blockIdx.x * kColTile + threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x;
     uint32_t a[kI], d[kI];
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -206,7 +190,7 @@ __global__ __launch_bounds__(kT) void k_col_cmp_mark(const uint32_t* __restrict_
     __shared__ uint32_t cnt[8];
     BlockCounts bc;
     bc.init(cnt);
-    const size_t base = (size_t)blockIdx.x * kColTile + threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x;
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
         const size_t j = base + (size_t)k * kT;
@@ -245,19 +229,6 @@ __global__ __launch_bounds__(kT) void k_col_cmp_apply(Cols c, uint32_t n_act, ui
 }
 
 // ---- scans -------------------------------------------------------------------------------------------------------------
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// ticket[a0 .. a0 + 8) of the tile-padded array, read once: non-temporal.
-__device__ __forceinline__ void stream_tickets(const int64_t* p, int64_t (&v)[kI]) {
-    const u32x4* q = reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-    for (uint32_t k = 0; k < kI / 2; ++k) {
-        const u32x4 w = __builtin_nontemporal_load(q + k);
-        v[2 * k] = (int64_t)((uint64_t)w.x | (uint64_t)w.y << 32);
-        v[2 * k + 1] = (int64_t)((uint64_t)w.z | (uint64_t)w.w << 32);
-    }
-}
-
 // What a scan does with entry a: 0 not a candidate, else the d_counts slot.
 constexpr uint32_t kScBadState = 1, kScKeptAlive = 2, kScActive = 3, kScYoung = 4, kScCondemned = 5, kScCancelled = 6;
 
@@ -290,9 +261,9 @@ __global__ __launch_bounds__(kT) void k_col_scan(Cols c, orl_act_state* __restri
     __shared__ uint32_t cnt[8];
     BlockCounts bc;
     if (kPlace) bc.init(cnt);
-    const uint32_t a0 = blockIdx.x * kColTile + threadIdx.x * kI;
+    const uint32_t a0 = blockIdx.x * kScanTile + threadIdx.x * kI;
     int64_t tk[kI];
-    stream_tickets(c.ticket + a0, tk);
+    stream_i64(c.ticket + a0, tk);  // ticket[a0 .. a0 + 8)
     uint32_t what[kI], fl[kI], mine = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -300,25 +271,13 @@ __global__ __launch_bounds__(kT) void k_col_scan(Cols c, orl_act_state* __restri
         what[k] = scan_decide<kAll>(c, state, a0 + k, tk[k], g, &fl[k]);
         mine += what[k] == kScCondemned;
     }
-    // inclusive Hillis-Steele scan of one count per thread
-    const uint32_t t = threadIdx.x;
-    uint32_t* src = lds;
-    uint32_t* dst = lds + kT;
-    src[t] = mine;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t d = 1; d < kT; d <<= 1) {
-        dst[t] = src[t] + (t >= d ? src[t - d] : 0u);
-        __syncthreads();
-        uint32_t* sw = src;
-        src = dst;
-        dst = sw;
-    }
+    uint32_t total;
+    const uint32_t ex = block_exclusive<uint32_t, OpAdd, kT>(mine, lds, &total);
     if (!kPlace) {
-        if (t == kT - 1) agg[blockIdx.x] = src[t];
+        if (threadIdx.x == 0) agg[blockIdx.x] = total;
         return;
     }
-    uint32_t pos = agg[blockIdx.x] + (t ? src[t - 1] : 0u);
+    uint32_t pos = agg[blockIdx.x] + ex;
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
         const uint32_t w = what[k], a = a0 + k;
@@ -350,39 +309,14 @@ __global__ __launch_bounds__(kT) void k_col_scan(Cols c, orl_act_state* __restri
     bc.flush(counts);
 }
 
-// In place: agg[i] = agg[0] + .. + agg[i - 1]; *total = the sum.  One workgroup; thread t owns a chunk.
+// In place: agg[i] = agg[0] + .. + agg[i - 1] (tile_scan_body); *total = the sum.
 __global__ __launch_bounds__(kScanThreads) void k_col_tilescan(uint32_t* __restrict__ agg, uint32_t ntiles,
                                                                uint64_t* __restrict__ total) {
     __shared__ uint32_t lds[2 * kScanThreads];
-    const uint32_t t = threadIdx.x;
-    const uint32_t chunk = (ntiles + kScanThreads - 1) / kScanThreads;
-    const uint32_t lo = t * chunk < ntiles ? t * chunk : ntiles;
-    const uint32_t hi = ntiles - lo < chunk ? ntiles : lo + chunk;
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; ++i) sum += agg[i];
-    uint32_t* src = lds;
-    uint32_t* dst = lds + kScanThreads;
-    src[t] = sum;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t d = 1; d < kScanThreads; d <<= 1) {
-        dst[t] = src[t] + (t >= d ? src[t - d] : 0u);
-        __syncthreads();
-        uint32_t* sw = src;
-        src = dst;
-        dst = sw;
-    }
-    uint32_t run = t ? src[t - 1] : 0u;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint32_t v = agg[i];
-        agg[i] = run;
-        run += v;
-    }
-    if (t == kScanThreads - 1) *total = src[t];
+    uint32_t sum;
+    tile_scan_body<uint32_t, uint32_t, OpAdd>(agg, ntiles, lds, &sum);
+    if (threadIdx.x == 0) *total = sum;
 }
-
-uint64_t pad_tile(uint64_t v) { return (v + kColTile - 1) / kColTile * kColTile; }
-uint64_t pad256(uint64_t v) { return (v + 255) / 256 * 256; }
 
 int zero_counts(uint64_t* d_counts, hipStream_t st) {
     if (!d_counts) return 0;
@@ -391,7 +325,7 @@ int zero_counts(uint64_t* d_counts, hipStream_t st) {
 
 template <bool kAll>
 int launch_scan(const orl_collector& c, orl_act_state* d_state, const ScanArgs& g, uint64_t* d_counts, hipStream_t st) {
-    const uint32_t tiles = (uint32_t)(pad_tile(c.n_act) / kColTile);
+    const uint32_t tiles = (uint32_t)(pad_to(c.n_act, kScanTile) / kScanTile);
     const Cols cols = cols_of(c);
     hipLaunchKernelGGL((k_col_scan<kAll, false>), dim3(tiles), dim3(kT), 0, st, cols, d_state, g, c.agg, c.out_act, d_counts);
     hipLaunchKernelGGL(k_col_tilescan, dim3(1), dim3(kScanThreads), 0, st, c.agg, tiles, c.out_n);
@@ -403,38 +337,35 @@ int launch_scan(const orl_collector& c, orl_act_state* d_state, const ScanArgs& 
 
 int collector_alloc(orl_collector** out, uint32_t n_act, uint64_t max_batch, int64_t quantum, int64_t next_ticket) {
     *out = nullptr;
-    const uint64_t np = pad_tile(n_act), tiles = np / kColTile;
-    const uint64_t b_i64 = np * 8, b_u8 = pad256(np), b_u32 = np * 4, b_agg = pad256(tiles * 4);
+    const uint64_t np = pad_to(n_act, kScanTile), tiles = np / kScanTile;
+    const uint64_t b_i64 = np * 8, b_u8 = np, b_u32 = np * 4, b_agg = pad_to(tiles * 4, 256);
     const uint64_t total = 4 * b_i64 + b_u8 + 2 * b_u32 + 256 + b_agg;
     void* base = nullptr;
     hipError_t e = hipMalloc(&base, total);
     if (e != hipSuccess) return (int)e;
     e = hipMemset(base, 0, total);
+    // the fill runs on the null stream and need not have finished; the first call may come on a non-blocking stream
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)hipFree(base);
         return (int)e;
     }
     orl_collector* c = new orl_collector();
-    uint8_t* p = static_cast<uint8_t*>(base);
-    auto take = [&p](uint64_t bytes) {
-        uint8_t* r = p;
-        p += bytes;
-        return r;
-    };
+    Carve cv(base);
     c->base = base;
     c->n_act = n_act;
     c->max_batch = max_batch;
     c->quantum = quantum;
     c->next_ticket = next_ticket;
-    c->ticket = reinterpret_cast<int64_t*>(take(b_i64));
-    c->became_idle = reinterpret_cast<int64_t*>(take(b_i64));
-    c->keep_alive_until = reinterpret_cast<int64_t*>(take(b_i64));
-    c->age_limit = reinterpret_cast<int64_t*>(take(b_i64));
-    c->cflags = take(b_u8);
-    c->out_act = reinterpret_cast<uint32_t*>(take(b_u32));
-    c->mark = reinterpret_cast<uint32_t*>(take(b_u32));
-    c->out_n = reinterpret_cast<uint64_t*>(take(256));
-    c->agg = reinterpret_cast<uint32_t*>(take(b_agg));
+    c->ticket = cv.take<int64_t>(b_i64);
+    c->became_idle = cv.take<int64_t>(b_i64);
+    c->keep_alive_until = cv.take<int64_t>(b_i64);
+    c->age_limit = cv.take<int64_t>(b_i64);
+    c->cflags = cv.take(b_u8);
+    c->out_act = cv.take<uint32_t>(b_u32);
+    c->mark = cv.take<uint32_t>(b_u32);
+    c->out_n = cv.take<uint64_t>(256);
+    c->agg = cv.take<uint32_t>(b_agg);
     *out = c;
     return 0;
 }
@@ -470,7 +401,7 @@ int launch_collect_touch(const orl_collector& c, const uint32_t* d_act, const ui
     hipStream_t st = (hipStream_t)stream;
     if (int e = zero_counts(d_counts, st)) return e;
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_col_touch_mark, dim3((uint32_t)((n + kColTile - 1) / kColTile)), dim3(kT), 0, st, d_act, d_disp, n,
+    hipLaunchKernelGGL(k_col_touch_mark, dim3((uint32_t)((n + kScanTile - 1) / kScanTile)), dim3(kT), 0, st, d_act, d_disp, n,
                        c.n_act, c.mark);
     hipLaunchKernelGGL(k_col_touch_apply, dim3((c.n_act + kT - 1) / kT), dim3(kT), 0, st, cols_of(c), c.n_act, c.mark, d_state,
                        limits.hard, limits.hard_stateless, now, c.quantum, c.next_ticket, d_counts);
@@ -482,7 +413,7 @@ int launch_collect_on_complete(const orl_collector& c, const uint32_t* d_cact, c
     hipStream_t st = (hipStream_t)stream;
     if (int e = zero_counts(d_counts, st)) return e;
     if (m == 0) return 0;
-    hipLaunchKernelGGL(k_col_cmp_mark, dim3((uint32_t)((m + kColTile - 1) / kColTile)), dim3(kT), 0, st, d_cact, d_ctok, m,
+    hipLaunchKernelGGL(k_col_cmp_mark, dim3((uint32_t)((m + kScanTile - 1) / kScanTile)), dim3(kT), 0, st, d_cact, d_ctok, m,
                        c.n_act, c.mark, d_counts);
     hipLaunchKernelGGL(k_col_cmp_apply, dim3((c.n_act + kT - 1) / kT), dim3(kT), 0, st, cols_of(c), c.n_act, c.mark, d_state,
                        now, c.quantum, c.next_ticket, d_counts);

@@ -251,6 +251,24 @@ inline uint64_t max_segments(uint64_t n, int hb) {
     return (n + s - 1) / s + std::min<uint64_t>(1ull << hb, n);
 }
 
+// ---- one device allocation carved into arrays (admit.hip, waitq.hip, collect.hip) ----------------------
+inline uint64_t pad_to(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
+
+// A cursor over a base pointer: take(bytes) gives the next array and steps past it.
+struct Carve {
+    uint8_t* p;
+    explicit Carve(void* base) : p(static_cast<uint8_t*>(base)) {}
+    template <class T = uint8_t>
+    T* take(uint64_t bytes) {
+        T* r = reinterpret_cast<T*>(p);
+        p += bytes;
+        return r;
+    }
+};
+
+// The stored per-tile aggregate of a segment scan (tile_scan_dev.h); the host side holds pointers to it only.
+struct SegAgg;
+
 // The directory partition table and the directory cache (AdaptiveGrainDirectoryCache) a route launch probes.
 // cache == nullptr / RouteParams.cache_on == 0: remote owners give ORL_ST_REMOTE_OWNER without a probe.
 // probe != nullptr: the compact probe table of `dir` is current and the route kernel probes it instead.

@@ -4,19 +4,6 @@
 
 #include "orl_internal.h"
 
-namespace orl {
-
-constexpr uint32_t kWqThreads = 256;
-constexpr uint32_t kWqItems = 8;
-constexpr uint32_t kWqTile = kWqThreads * kWqItems;  // positions / records per workgroup
-
-// A scan value (waitq.hip gives the two scans their meaning); one per tile in orl_waitq::agg.
-struct WqSeg {
-    uint32_t a, b, f, pad;
-};
-
-}  // namespace orl
-
 // One queue object: the store (double-buffered CSR), running_tok, the out list and the scratch of its calls, all carved
 // from one device allocation (`base`).  Per-record arrays are padded to whole tiles.
 struct orl_waitq {
@@ -43,7 +30,7 @@ struct orl_waitq {
     uint32_t* pre = nullptr;   // [max(max_batch, capacity) + 1] exclusive count before a position / record, and the total
     uint32_t* mark = nullptr;  // [n_act] complete: kWqMark* of the activation's records
     uint32_t* nonc = nullptr;  // [n_act] complete: its pump and drain records (k = its bucket's length - nonc)
-    orl::WqSeg* agg = nullptr;  // [tiles] per-tile aggregates, then their exclusive scan
+    orl::SegAgg* agg = nullptr;  // [tiles] per-tile aggregates, then their exclusive scan
 };
 
 namespace orl {

@@ -36,14 +36,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include "tile_scan_dev.h"
 #include "waitq.h"
 
 namespace orl {
 
 namespace {
 
-constexpr uint32_t kT = kWqThreads, kI = kWqItems;
-constexpr uint32_t kScanThreads = 1024;  // k_wq_tilescan's one workgroup
+constexpr uint32_t kT = kTileThreads, kI = kTileItems;
 
 // cls[p] of append
 constexpr uint32_t kAppEnq = 0x01, kAppRun = 0x02, kAppHead = 0x04;
@@ -51,10 +51,6 @@ constexpr uint32_t kAppEnq = 0x01, kAppRun = 0x02, kAppHead = 0x04;
 constexpr uint32_t kCmpFail = 0x01, kCmpHead = 0x02, kCmpDrained = 0x04;
 // mark[a]
 constexpr uint32_t kMarkR = 0x01, kMarkPump = 0x02, kMarkDrain = 0x04;
-
-struct Seg {
-    uint32_t a, b, f;
-};
 
 // Append's scan.  a = ENQUEUEs (never reset), b = 1: a RUN since the span's last bucket head, f = 1: holds a head.
 struct OpApp {
@@ -90,134 +86,20 @@ __device__ __forceinline__ Seg seg_out(uint32_t cls) {
     return Seg{0u, ok, ok ? 0u : 2u};
 }
 
-// Inclusive Hillis-Steele scan of one value per thread through LDS (2 * N values); returns the exclusive prefix of
-// thread t and the workgroup's total.  Ends on a barrier: `lds` may be reused at once.
-template <class Op, uint32_t N>
-__device__ __forceinline__ Seg block_exclusive(Seg mine, Seg* lds, Seg* total) {
-    const uint32_t t = threadIdx.x;
-    Seg* src = lds;
-    Seg* dst = lds + N;
-    src[t] = mine;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t d = 1; d < N; d <<= 1) {
-        Seg v = src[t];
-        if (t >= d) v = Op::op(src[t - d], v);
-        dst[t] = v;
-        __syncthreads();
-        Seg* sw = src;
-        src = dst;
-        dst = sw;
-    }
-    const Seg ex = t ? src[t - 1] : Seg{0, 0, 0};
-    *total = src[N - 1];
-    __syncthreads();
-    return ex;
-}
-
-// The 8 bytes / 8 words of thread t's items in a tile-padded array.
-__device__ __forceinline__ void load_bytes(const uint8_t* p, uint32_t (&v)[kI]) {
-    const uint2 w = *reinterpret_cast<const uint2*>(p);
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        v[k] = (w.x >> (8 * k)) & 0xFFu;
-        v[k + 4] = (w.y >> (8 * k)) & 0xFFu;
-    }
-}
-
-__device__ __forceinline__ void store_bytes(uint8_t* p, const uint32_t (&v)[kI]) {
-    uint2 w;
-    w.x = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-    w.y = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
-    *reinterpret_cast<uint2*>(p) = w;
-}
-
-__device__ __forceinline__ void load_words(const uint32_t* p, uint32_t (&v)[kI]) {
-    const uint4 lo = *reinterpret_cast<const uint4*>(p), hi = *reinterpret_cast<const uint4*>(p + 4);
-    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-    v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-}
-
-// The same of a store array (tile-padded, 16-byte aligned), read once: non-temporal.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void stream_words(const uint32_t* p, uint32_t (&v)[kI]) {
-    const u32x4 lo = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    const u32x4 hi = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + 4));
-    v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-    v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-}
-
-__device__ __forceinline__ void stream_bytes(const uint8_t* p, uint32_t (&v)[kI]) {
-    const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) {
-        v[k] = (w.x >> (8 * k)) & 0xFFu;
-        v[k + 4] = (w.y >> (8 * k)) & 0xFFu;
-    }
-}
-
-// order[p0 .. p0 + 8) of the caller's array, streamed (non-temporal); 0 past n.
-__device__ __forceinline__ void load_order(const uint32_t* __restrict__ order, size_t p0, size_t n, bool vec,
-                                           uint32_t (&v)[kI]) {
-    if (vec && p0 + kI <= n) {
-        stream_words(order + p0, v);
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < kI; ++k) v[k] = p0 + k < n ? __builtin_nontemporal_load(order + p0 + k) : 0u;
-    }
-}
-
-// The bucket of position p: the smallest b in [lo, n_act] with off[b + 1] > p (off[n_act + 1] = n > p).  At most 32 steps.
-__device__ __forceinline__ uint32_t bucket_of(const uint32_t* __restrict__ off, uint32_t lo, uint32_t n_act, size_t p) {
-    uint32_t hi = n_act;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if ((size_t)off[mid + 1] > p) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 // ---- append ----------------------------------------------------------------------------------------------------------
 // The key of a position comes from the offsets, as in admission: a search per thread and one more per
 // bucket boundary inside its 8 positions (the next bucket first).
 __global__ __launch_bounds__(kT) void k_wq_app_classify(const uint8_t* __restrict__ disp, size_t n, uint32_t n_act,
                                                         const uint32_t* __restrict__ order, bool order_vec,
                                                         const uint32_t* __restrict__ off, uint32_t* __restrict__ key_out,
-                                                        uint8_t* __restrict__ cls_out, WqSeg* __restrict__ agg) {
+                                                        uint8_t* __restrict__ cls_out, SegAgg* __restrict__ agg) {
     __shared__ Seg lds[2 * kT];
-    const size_t p0 = (size_t)blockIdx.x * kWqTile + (size_t)threadIdx.x * kI;
+    const size_t p0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     uint32_t idx[kI], key[kI], cls[kI], head = 0;
     load_order(order, p0, n, order_vec, idx);
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) cls[k] = p0 + k < n ? disp[idx[k]] : 0xFFu;  // 8 gathers in flight together
-    uint32_t b = n_act;
-    size_t begin = 0, end = 0;  // bucket b = [begin, end)
-    if (p0 < n) {
-        b = bucket_of(off, 0, n_act, p0);
-        begin = off[b];
-        end = off[b + 1];
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < kI; ++k) {
-        const size_t p = p0 + k;
-        if (p < n && p >= end && b < n_act) {  // the last bucket ends at n: b < n_act holds for stage 4's offsets
-            const size_t next_end = off[b + 2];
-            if (p < next_end) {
-                b += 1;
-                begin = end;
-                end = next_end;
-            } else {
-                b = bucket_of(off, b + 2 < n_act ? b + 2 : n_act, n_act, p);
-                begin = off[b];
-                end = off[b + 1];
-            }
-        }
-        key[k] = p < n ? b : n_act;
-        head |= (p < n && p == begin ? 1u : 0u) << k;
-    }
+    bucket_keys(off, n_act, p0, n, key, &head);
     Seg sum{0, 0, 0};
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -231,40 +113,26 @@ __global__ __launch_bounds__(kT) void k_wq_app_classify(const uint8_t* __restric
     ko[1] = make_uint4(key[4], key[5], key[6], key[7]);
     store_bytes(cls_out + p0, cls);
     Seg total;
-    (void)block_exclusive<OpApp, kT>(sum, lds, &total);
-    if (threadIdx.x == 0) agg[blockIdx.x] = WqSeg{total.a, total.b, total.f, 0};
+    (void)block_exclusive<Seg, OpApp, kT>(sum, lds, &total);
+    if (threadIdx.x == 0) agg[blockIdx.x] = SegAgg(total);
 }
 
-// In place: agg[i] = the fold of agg[0 .. i).  One workgroup; thread t owns the chunk [t * chunk, (t + 1) * chunk).
+// In place: agg[i] = the fold of agg[0 .. i) (tile_scan_body).
 template <class Op>
-__global__ __launch_bounds__(kScanThreads) void k_wq_tilescan(WqSeg* __restrict__ agg, uint32_t ntiles) {
+__global__ __launch_bounds__(kScanThreads) void k_wq_tilescan(SegAgg* __restrict__ agg, uint32_t ntiles) {
     __shared__ Seg lds[2 * kScanThreads];
-    const uint32_t chunk = (ntiles + kScanThreads - 1) / kScanThreads;
-    const uint32_t lo = threadIdx.x * chunk < ntiles ? threadIdx.x * chunk : ntiles;
-    const uint32_t hi = ntiles - lo < chunk ? ntiles : lo + chunk;
-    Seg sum{0, 0, 0};
-    for (uint32_t i = lo; i < hi; ++i) {
-        const WqSeg v = agg[i];
-        sum = Op::op(sum, Seg{v.a, v.b, v.f});
-    }
-    Seg total;
-    Seg run = block_exclusive<Op, kScanThreads>(sum, lds, &total);
-    for (uint32_t i = lo; i < hi; ++i) {
-        const WqSeg v = agg[i];
-        agg[i] = WqSeg{run.a, run.b, run.f, 0};
-        run = Op::op(run, Seg{v.a, v.b, v.f});
-    }
+    tile_scan_body<Seg, SegAgg, Op>(agg, ntiles, lds);
 }
 
 __global__ __launch_bounds__(kT) void k_wq_app_scatter(const uint32_t* __restrict__ tok, const uint8_t* __restrict__ mflags,
                                                        size_t n, const uint32_t* __restrict__ order, bool order_vec,
                                                        const uint32_t* __restrict__ key_in, const uint8_t* __restrict__ cls_in,
-                                                       const WqSeg* __restrict__ carry, const uint32_t* __restrict__ old_off,
+                                                       const SegAgg* __restrict__ carry, const uint32_t* __restrict__ old_off,
                                                        uint32_t* __restrict__ new_tok, uint32_t* __restrict__ new_act,
                                                        uint8_t* __restrict__ new_mflags, uint32_t* __restrict__ running_tok,
                                                        uint32_t* __restrict__ pre) {
     __shared__ Seg lds[2 * kT];
-    const size_t p0 = (size_t)blockIdx.x * kWqTile + (size_t)threadIdx.x * kI;
+    const size_t p0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     uint32_t idx[kI], key[kI], cls[kI];
     load_order(order, p0, n, order_vec, idx);
     load_words(key_in + p0, key);
@@ -273,9 +141,9 @@ __global__ __launch_bounds__(kT) void k_wq_app_scatter(const uint32_t* __restric
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) sum = OpApp::op(sum, seg_app(cls[k]));
     Seg total;
-    const Seg ex = block_exclusive<OpApp, kT>(sum, lds, &total);
-    const WqSeg cin = carry[blockIdx.x];
-    Seg run = OpApp::op(Seg{cin.a, cin.b, cin.f}, ex);
+    const Seg ex = block_exclusive<Seg, OpApp, kT>(sum, lds, &total);
+    const SegAgg cin = carry[blockIdx.x];
+    Seg run = OpApp::op(Seg(cin), ex);
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
         const uint32_t c = cls[k];
@@ -312,7 +180,7 @@ __global__ __launch_bounds__(kT) void k_wq_app_move(uint32_t n_act, const uint32
                                                     const uint32_t* __restrict__ old_act, const uint8_t* __restrict__ old_mflags,
                                                     uint32_t* __restrict__ new_tok, uint32_t* __restrict__ new_act,
                                                     uint8_t* __restrict__ new_mflags) {
-    const size_t i0 = (size_t)blockIdx.x * kWqTile + (size_t)threadIdx.x * kI;
+    const size_t i0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     const size_t len = old_off[n_act];
     if (i0 >= len) return;
     uint32_t t[kI], a[kI], f[kI];
@@ -339,7 +207,7 @@ __global__ __launch_bounds__(kT) void k_wq_mark(const uint32_t* __restrict__ cac
     __shared__ uint32_t cnt_lds[4];
     if (threadIdx.x < 4) cnt_lds[threadIdx.x] = 0;
     __syncthreads();
-    const size_t base = (size_t)blockIdx.x * kWqTile + threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x;
     uint32_t kind[kI];
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) {
@@ -363,22 +231,7 @@ __global__ __launch_bounds__(kT) void k_wq_mark(const uint32_t* __restrict__ cac
             }
         }
     }
-    if (counts) {  // uniform; every lane of the wave reaches the ballots
-        uint32_t wc[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t k = 0; k < kI; ++k) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) wc[q] += (uint32_t)__popcll(__ballot(kind[k] == q));
-        }
-        if ((threadIdx.x & 63u) == 0) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q)
-                if (wc[q]) atomicAdd(&cnt_lds[q], wc[q]);
-        }
-        __syncthreads();
-        if (threadIdx.x < 4 && cnt_lds[threadIdx.x])
-            atomicAdd(reinterpret_cast<unsigned long long*>(counts + threadIdx.x), (unsigned long long)cnt_lds[threadIdx.x]);
-    }
+    if (counts) ballot_counts<4>(kind, cnt_lds, counts);  // uniform; every lane of the wave reaches the ballots
 }
 
 // An activation's state after steps 1-2 (all its completions applied), from its entry, marks and bucket.
@@ -408,9 +261,9 @@ __global__ __launch_bounds__(kT) void k_wq_cmp_classify(uint32_t n_act, const ui
                                                         const uint32_t* __restrict__ cboff, const uint32_t* __restrict__ mark,
                                                         const uint32_t* __restrict__ nonc,
                                                         const orl_act_state* __restrict__ state,
-                                                        uint8_t* __restrict__ cls_out, WqSeg* __restrict__ agg) {
+                                                        uint8_t* __restrict__ cls_out, SegAgg* __restrict__ agg) {
     __shared__ Seg lds[2 * kT];
-    const size_t i0 = (size_t)blockIdx.x * kWqTile + (size_t)threadIdx.x * kI;
+    const size_t i0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     const size_t len = off[n_act];
     uint32_t a[kI], f[kI], cls[kI];
     stream_words(act + i0, a);
@@ -449,20 +302,20 @@ __global__ __launch_bounds__(kT) void k_wq_cmp_classify(uint32_t n_act, const ui
     }
     store_bytes(cls_out + i0, cls);
     Seg total;
-    (void)block_exclusive<OpOut, kT>(sum, lds, &total);
-    if (threadIdx.x == 0) agg[blockIdx.x] = WqSeg{total.a, total.b, total.f, 0};
+    (void)block_exclusive<Seg, OpOut, kT>(sum, lds, &total);
+    if (threadIdx.x == 0) agg[blockIdx.x] = SegAgg(total);
 }
 
 __global__ __launch_bounds__(kT) void k_wq_cmp_resolve(uint32_t n_act, const uint32_t* __restrict__ off,
                                                        const uint32_t* __restrict__ tok, const uint32_t* __restrict__ act,
                                                        const uint8_t* __restrict__ mflags, const uint8_t* __restrict__ cls_in,
-                                                       const WqSeg* __restrict__ carry, uint32_t* __restrict__ new_tok,
+                                                       const SegAgg* __restrict__ carry, uint32_t* __restrict__ new_tok,
                                                        uint32_t* __restrict__ new_act, uint8_t* __restrict__ new_mflags,
                                                        uint32_t* __restrict__ out_tok, uint32_t* __restrict__ out_act,
                                                        uint8_t* __restrict__ out_mflags, uint8_t* __restrict__ out_kind,
                                                        uint32_t* __restrict__ pre) {
     __shared__ Seg lds[2 * kT];
-    const size_t i0 = (size_t)blockIdx.x * kWqTile + (size_t)threadIdx.x * kI;
+    const size_t i0 = (size_t)blockIdx.x * kScanTile + (size_t)threadIdx.x * kI;
     const size_t len = off[n_act];
     uint32_t t[kI], a[kI], f[kI], cls[kI];
     stream_words(tok + i0, t);
@@ -473,9 +326,9 @@ __global__ __launch_bounds__(kT) void k_wq_cmp_resolve(uint32_t n_act, const uin
 #pragma unroll
     for (uint32_t k = 0; k < kI; ++k) sum = OpOut::op(sum, seg_out(cls[k]));
     Seg total;
-    const Seg ex = block_exclusive<OpOut, kT>(sum, lds, &total);
-    const WqSeg cin = carry[blockIdx.x];
-    const Seg p = OpOut::op(Seg{cin.a, cin.b, cin.f}, ex);
+    const Seg ex = block_exclusive<Seg, OpOut, kT>(sum, lds, &total);
+    const SegAgg cin = carry[blockIdx.x];
+    const Seg p = OpOut::op(Seg(cin), ex);
     uint32_t cnt = p.a + p.b;  // nothing is carried into record 0
     bool failed = (p.f & 2u) != 0;
 #pragma unroll
@@ -557,8 +410,7 @@ __global__ __launch_bounds__(kT) void k_wq_cmp_finish(uint32_t n_act, int scanne
     }
     if (counts) {
         __syncthreads();
-        if (threadIdx.x < 3 && cnt_lds[threadIdx.x])
-            atomicAdd(reinterpret_cast<unsigned long long*>(counts + 4 + threadIdx.x), (unsigned long long)cnt_lds[threadIdx.x]);
+        flush_counts<3>(cnt_lds, counts + 4);
     }
 }
 
@@ -569,54 +421,48 @@ __global__ void k_wq_cmp_empty(uint32_t n_act, const uint32_t* __restrict__ off,
     if (counts) counts[7] = off[n_act];
 }
 
-uint64_t pad_tile(uint64_t v) { return (v + kWqTile - 1) / kWqTile * kWqTile; }
-uint64_t pad256(uint64_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 int waitq_alloc(orl_waitq** out, uint32_t n_act, uint64_t capacity, uint64_t max_batch) {
     *out = nullptr;
-    const uint64_t cap = pad_tile(capacity ? capacity : 1), batch = pad_tile(max_batch ? max_batch : 1);
-    const uint64_t big = cap > batch ? cap : batch, tiles = big / kWqTile;
-    const uint64_t b_off = pad256(((uint64_t)n_act + 1) * 4), b_w = cap * 4, b_b = cap, b_act = pad256((uint64_t)n_act * 4);
-    const uint64_t b_key = batch * 4, b_cls = big, b_pre = pad256((big + 1) * 4), b_agg = pad256(tiles * sizeof(WqSeg));
+    const uint64_t cap = pad_to(capacity ? capacity : 1, kScanTile), batch = pad_to(max_batch ? max_batch : 1, kScanTile);
+    const uint64_t big = cap > batch ? cap : batch, tiles = big / kScanTile;
+    const uint64_t b_off = pad_to(((uint64_t)n_act + 1) * 4, 256), b_w = cap * 4, b_b = cap, b_act = pad_to((uint64_t)n_act * 4, 256);
+    const uint64_t b_key = batch * 4, b_cls = big, b_pre = pad_to((big + 1) * 4, 256), b_agg = pad_to(tiles * sizeof(SegAgg), 256);
     const uint64_t total = 2 * (b_off + 2 * b_w + b_b) + b_act + (2 * b_w + 2 * b_b) + 256 + b_key + b_cls + b_pre +
                            2 * b_act + b_agg;
     void* base = nullptr;
     hipError_t e = hipMalloc(&base, total);
     if (e != hipSuccess) return (int)e;
     orl_waitq* q = new orl_waitq();
-    uint8_t* p = static_cast<uint8_t*>(base);
-    auto take = [&p](uint64_t bytes) {
-        uint8_t* r = p;
-        p += bytes;
-        return r;
-    };
+    Carve c(base);
     q->base = base;
     q->capacity = capacity;
     q->max_batch = max_batch;
     q->n_act = n_act;
     for (int i = 0; i < 2; ++i) {
-        q->off[i] = reinterpret_cast<uint32_t*>(take(b_off));
-        q->tok[i] = reinterpret_cast<uint32_t*>(take(b_w));
-        q->act[i] = reinterpret_cast<uint32_t*>(take(b_w));
-        q->mflags[i] = take(b_b);
+        q->off[i] = c.take<uint32_t>(b_off);
+        q->tok[i] = c.take<uint32_t>(b_w);
+        q->act[i] = c.take<uint32_t>(b_w);
+        q->mflags[i] = c.take(b_b);
     }
-    q->running_tok = reinterpret_cast<uint32_t*>(take(b_act));
-    q->out_tok = reinterpret_cast<uint32_t*>(take(b_w));
-    q->out_act = reinterpret_cast<uint32_t*>(take(b_w));
-    q->out_mflags = take(b_b);
-    q->out_kind = take(b_b);
-    q->out_n = reinterpret_cast<uint64_t*>(take(256));
+    q->running_tok = c.take<uint32_t>(b_act);
+    q->out_tok = c.take<uint32_t>(b_w);
+    q->out_act = c.take<uint32_t>(b_w);
+    q->out_mflags = c.take(b_b);
+    q->out_kind = c.take(b_b);
+    q->out_n = c.take<uint64_t>(256);
     q->waiting_n = q->out_n + 1;
-    q->key = reinterpret_cast<uint32_t*>(take(b_key));
-    q->cls = take(b_cls);
-    q->pre = reinterpret_cast<uint32_t*>(take(b_pre));
-    q->mark = reinterpret_cast<uint32_t*>(take(b_act));  // mark and nonc are cleared together
-    q->nonc = reinterpret_cast<uint32_t*>(take(b_act));
-    q->agg = reinterpret_cast<WqSeg*>(take(b_agg));
+    q->key = c.take<uint32_t>(b_key);
+    q->cls = c.take(b_cls);
+    q->pre = c.take<uint32_t>(b_pre);
+    q->mark = c.take<uint32_t>(b_act);  // mark and nonc are cleared together
+    q->nonc = c.take<uint32_t>(b_act);
+    q->agg = c.take<SegAgg>(b_agg);
     e = hipMemset(base, 0, total);
     if (e == hipSuccess) e = hipMemset(q->running_tok, 0xFF, b_act);
+    // the fills run on the null stream and need not have finished; the first call may come on a non-blocking stream
+    if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         waitq_free(q);
         return (int)e;
@@ -635,7 +481,7 @@ int launch_waitq_append(const orl_waitq& q, uint64_t old_bound, const uint32_t* 
                         const uint32_t* d_order, const uint32_t* d_boff, const uint8_t* d_disp, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const uint32_t c = q.cur, o = c ^ 1u;
-    const uint32_t tiles = (uint32_t)((n + kWqTile - 1) / kWqTile);
+    const uint32_t tiles = (uint32_t)((n + kScanTile - 1) / kScanTile);
     const bool order_vec = ((uintptr_t)d_order & 15u) == 0;
     hipLaunchKernelGGL(k_wq_app_classify, dim3(tiles), dim3(kT), 0, st, d_disp, n, q.n_act, d_order, order_vec, d_boff,
                        q.key, q.cls, q.agg);
@@ -645,7 +491,7 @@ int launch_waitq_append(const orl_waitq& q, uint64_t old_bound, const uint32_t* 
     hipLaunchKernelGGL(k_wq_app_offsets, dim3(q.n_act / kT + 1), dim3(kT), 0, st, q.n_act, d_boff, q.pre, q.off[c], q.off[o],
                        q.waiting_n);
     if (old_bound) {
-        const uint32_t rtiles = (uint32_t)((old_bound + kWqTile - 1) / kWqTile);
+        const uint32_t rtiles = (uint32_t)((old_bound + kScanTile - 1) / kScanTile);
         hipLaunchKernelGGL(k_wq_app_move, dim3(rtiles), dim3(kT), 0, st, q.n_act, q.off[c], q.off[o], q.tok[c], q.act[c],
                            q.mflags[c], q.tok[o], q.act[o], q.mflags[o]);
     }
@@ -666,10 +512,10 @@ int launch_waitq_complete(const orl_waitq& q, const uint32_t* d_cact, const uint
     }
     hipError_t e = hipMemsetAsync(q.mark, 0, (size_t)((uint8_t*)q.agg - (uint8_t*)q.mark), st);  // mark and nonc
     if (e != hipSuccess) return (int)e;
-    const uint32_t mtiles = (uint32_t)((m + kWqTile - 1) / kWqTile);
+    const uint32_t mtiles = (uint32_t)((m + kScanTile - 1) / kScanTile);
     hipLaunchKernelGGL(k_wq_mark, dim3(mtiles), dim3(kT), 0, st, d_cact, d_ctok, m, q.n_act, q.running_tok, q.mark, q.nonc,
                        d_counts);
-    const uint32_t rtiles = (uint32_t)((q.bound + kWqTile - 1) / kWqTile);
+    const uint32_t rtiles = (uint32_t)((q.bound + kScanTile - 1) / kScanTile);
     if (rtiles) {
         hipLaunchKernelGGL(k_wq_cmp_classify, dim3(rtiles), dim3(kT), 0, st, q.n_act, q.off[c], q.act[c], q.mflags[c], d_cboff,
                            q.mark, q.nonc, d_state, q.cls, q.agg);

@@ -75,6 +75,7 @@ def run(eng, n_act, n, reps, warm, stream, dev):
 
     def fresh(idle):
         box["col"] = col = eng.collector_create(QT, T0)
+        torch.cuda.synchronize()  # a build before DESIGN §19 returned with its zero-fill still running on the null stream
         v = eng.collector_view(col)
         for p, src in ((v.d_ticket, ticket0), (v.d_age_limit, age0), (v.d_became_idle, idle)):
             eng.copy_on_device(p, src, 8 * n_act, stream=sp)

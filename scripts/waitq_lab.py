@@ -86,6 +86,7 @@ def main(reps=20, warm=3, log_n=26, log_act=20):
 
         def fresh(appended):
             box["q"] = eng.waitq_create(n)
+            torch.cuda.synchronize()  # a build before DESIGN §19 returned with its fills still running on the null stream
             if appended:
                 eng.waitq_append_device(box["q"], tok, mflags, n, order, off, disp, stream=sp)
                 d_state.copy_(d_state_adm)

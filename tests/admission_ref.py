@@ -292,6 +292,31 @@ def all_scenarios():
     return out
 
 
+# ---- the chunked regime of the one-workgroup tile scan ---------------------------------------------------------------
+# More tiles (2048 positions) than the scan workgroup has threads (1024): a thread owns a chunk of ceil(tiles / 1024)
+# aggregates.  Exactly 1024 tiles (chunk 1, every thread busy), 1025 (chunk 2, the last working thread owns one
+# aggregate) and 2049 (chunk 3).  tests/test_source_layout.py holds these to the constants in tile_scan_dev.h.  The
+# loop above is too slow at 4 M messages; the GPU tests compare these with admit_closed_form below.
+CHUNK_N = (1024 * 2048, 1024 * 2048 + 1, 2048 * 2048 + 1)
+CHUNK_STRIDE = 3000  # a bucket head every 3000 positions: 3000 k is a multiple of 2048 only for every 256th head
+
+
+def chunk_scenarios(n):
+    """Two batches of n messages.  `one`: the whole batch in one bucket (handle 1 of 3, as one_bucket_scenarios), which
+    saturates after n // 2 requests: some 60 % into the batch, many chunks behind the bucket head at position 0.
+    `stride`: bucket b holds the positions [3000 b, 3000 b + 3000), arrival order shuffled, random states, and limits that
+    saturate a bucket half-way."""
+    rng = np.random.default_rng([n, 1024])
+    busy = L.ACTF_RUNNING_SET | L.ACTF_RUNNING_RO
+    one = Scenario(f"chunk-one-n{n}", 3, np.full(n, 1, np.uint32), random_flags(rng, n, p_ro=0.3, p_ai=0.02, p_exp=0.03),
+                   _valid(3, 1, busy, 2, 2, 1), 3 + n // 2, 9)
+    n_act = (n + CHUNK_STRIDE - 1) // CHUNK_STRIDE
+    act = rng.permutation((np.arange(n) // CHUNK_STRIDE).astype(np.uint32))
+    stride = Scenario(f"chunk-stride-n{n}", n_act, act, random_flags(rng, n, p_ro=0.3), random_state(rng, n_act),
+                      CHUNK_STRIDE // 2, CHUNK_STRIDE // 3)
+    return [one, stride]
+
+
 # ---- the closed form (DESIGN §16), vectorised per bucket: what the kernels compute, stated in numpy ------------------
 def admit_closed_form(act, mflags, state, n_act, hard=0, hard_stateless=0):
     """The same three results from per-bucket prefix counts instead of the loop (tests hold it to admit)."""

@@ -648,6 +648,10 @@ def fresh_col(n_act, age=2 * QUANTUM, now0=T0):
 
 
 GPU_N_ACT = (1, 5, 2047, 2048, 2049, 5000, 1 << 20)
+# The chunked regime of the one-workgroup tile scan (admission_ref.CHUNK_N): 1024, 1025 and 2049 tiles of activations, so
+# that a scan thread owns 1, 2 and 3 tile counts.  Compared with the numpy form only.
+CHUNK_N_ACT = A.CHUNK_N
+CHUNK_DENSITIES = ("one-per-tile", "all")
 
 
 def density_scenario(n_act, density):

@@ -241,9 +241,10 @@ def complete(w, cact, ctok, cov=None, perm=None):
     return nw, out, counts
 
 
-def complete_closed_form(w, cact, ctok):
+def complete_closed_form(w, cact, ctok, as_arrays=False):
     """The same from the closed form, in numpy over the whole store: apply all completions, then a record is
-    taken iff no record at or before it in its segment fails."""
+    taken iff no record at or before it in its segment fails.  as_arrays: the out list as its four columns (tok, act,
+    mflags, kind) instead of a list of tuples, for stores of millions of records."""
     n_act = w.n_act
     cact, ctok = np.asarray(cact, np.uint32).astype(np.int64), np.asarray(ctok, np.uint32)
     counts = np.zeros(8, np.uint64)
@@ -285,8 +286,10 @@ def complete_closed_form(w, cact, ctok):
     before_head = np.concatenate([[0], cf])[off[act]]
     out_mask = (cf - before_head) == 0
     taken = np.bincount(act[out_mask], minlength=n_act)
-    out = [(int(w.tok[i]), int(act[i]), int(mf[i]), L.WQ_DRAINED if drain[act[i]] else L.WQ_RUN)
-           for i in np.nonzero(out_mask)[0]]
+    oi = np.nonzero(out_mask)[0]
+    out = (w.tok[oi], act[oi].astype(np.uint32), w.mflags[oi], np.where(drain[act[oi]], L.WQ_DRAINED, L.WQ_RUN).astype(np.uint8))
+    if not as_arrays:
+        out = [tuple(int(x) for x in o) for o in zip(*out)]
     counts[L.CMP_DRAINED] = int(taken[drain].sum())
     counts[L.CMP_RUN] = int(taken[~drain].sum())
     pumped = touched & ~drain & (taken > 0)
@@ -525,6 +528,78 @@ def drain_pump_scenario():
     cact = [0, 1, 1, 2, 3, 3, 3, 4, 5, 6, 6, 7, n_act, U32, 8, 8, 9, 9]
     ctok = [DRAIN, DRAIN, 901, NONE, 903, NONE, NONE, NONE, 905, 906, 55, 56, 1, NONE, NONE, DRAIN, 909, 57]
     return Scenario("drain-pump", w, [], [], cact, ctok)
+
+
+# ---- the chunked regime of the one-workgroup tile scan (admission_ref.CHUNK_N has the shapes) --------------------------
+# The loops above are too slow at 4 M records; the GPU tests compare these with append_ref and complete_closed_form.
+CHUNK_N = A.CHUNK_N
+CHUNK_STRIDE = A.CHUNK_STRIDE
+
+
+def _chunk_acts(n, kind):
+    """`one`: handle 1 of 3 holds all n positions; `stride`: handle a holds [3000 a, 3000 a + 3000)."""
+    if kind == "one":
+        return 3, np.full(n, 1, np.uint32)
+    return (n + CHUNK_STRIDE - 1) // CHUNK_STRIDE, (np.arange(n) // CHUNK_STRIDE).astype(np.uint32)
+
+
+def chunk_appends(n):
+    """-> [(name, World, act, tok, mflags, disp)]: an empty store and a batch of n positions with dispositions drawn at
+    random (half ENQUEUE, a fifth RUN).  `one`: the bucket's first RUN lies behind n // 2, so "a RUN was seen" crosses
+    many chunks and every later RUN must leave running_tok alone.  `stride`: arrival order shuffled, and every third
+    activation already has a Running."""
+    out = []
+    for kind in ("one", "stride"):
+        rng = np.random.default_rng([n, 1024, kind == "one"])
+        n_act, act = _chunk_acts(n, kind)
+        s = np.zeros(n_act, STATE_DTYPE)
+        s["state"] = L.ACT_VALID
+        rt = np.full(n_act, NONE, np.uint32)
+        disp = rng.choice(np.array([L.ADM_ENQUEUE, L.ADM_RUN, L.ADM_OVERLOADED, L.ADM_RESPONSE, L.ADM_EXPIRED], np.uint8), n,
+                          p=[0.5, 0.2, 0.1, 0.1, 0.1])
+        if kind == "one":
+            early = np.arange(n) < n // 2 + 5
+            disp[early & (disp == L.ADM_RUN)] = L.ADM_RESPONSE
+        else:
+            act = rng.permutation(act)
+            rt[::3] = (0x20000000 + np.arange(n_act))[::3]
+        tok = (0x50000000 + np.arange(n)).astype(np.uint32)
+        out.append((f"chunk-append-{kind}-n{n}", World(s, running_tok=rt), act, tok, request_flags(rng, n), disp))
+    return out
+
+
+def chunk_completes(n):
+    """-> [(name, World, cact, ctok)]: a store of n records.  `one`: Running is a read-only request and the records are
+    read-only up to the first read-write one at n // 2 + 77, so the pump takes a prefix that ends many chunks behind the
+    segment's head.  `stride`: random tables (half of the activations reentrant: their whole segment goes, across a tile
+    edge), three activations of four get a record: a completion (Running's own for every other one), a pump or a drain."""
+    out = []
+    busy = L.ACTF_RUNNING_SET | L.ACTF_RUNNING_RO
+    fl = np.full(n, L.MF_REQUEST | L.MF_READ_ONLY, np.uint8)
+    fl[n // 2 + 77] = fl[n // 2 + 82] = L.MF_REQUEST
+    out.append((f"chunk-complete-one-n{n}", _one_act_world(3, 1, busy, 2, fl, rt=77), np.array([1], np.uint32),
+                np.array([0x10000000], np.uint32)))
+    rng = np.random.default_rng([n, 1024, 7])
+    n_act, act = _chunk_acts(n, "stride")
+    s = np.zeros(n_act, STATE_DTYPE)
+    s["state"] = np.where(rng.random(n_act) < 0.9, L.ACT_VALID, L.ACT_DEACTIVATING)
+    s["flags"] = rng.integers(0, 16, n_act)
+    s["num_running"] = rng.integers(0, 3, n_act)
+    s["in_flight"] = s["num_running"] + rng.integers(0, 2, n_act)
+    s["waiting"] = np.bincount(act, minlength=n_act)
+    off = np.concatenate([[0], np.cumsum(s["waiting"])]).astype(np.uint32)
+    h = np.arange(n_act)
+    rt = np.where(s["flags"] & L.ACTF_RUNNING_SET, 0x20000000 + h, NONE).astype(np.uint32)
+    w = World(s, off, (0x40000000 + np.arange(n)).astype(np.uint32), request_flags(rng, n, p_ro=0.9, p_ai=0.05), rt)
+    cact = h[h % 4 != 3].astype(np.uint32)
+    ctok = np.where((cact % 2 == 1) & (rt[cact] != NONE), rt[cact], 0x10000000 + cact).astype(np.uint32)
+    ctok[cact % 16 == 5] = NONE
+    ctok[cact % 32 == 9] = DRAIN
+    cact = np.concatenate([cact, np.array([n_act, U32], np.uint32)])
+    ctok = np.concatenate([ctok, np.array([1, NONE], np.uint32)])
+    p = rng.permutation(len(cact))
+    out.append((f"chunk-complete-stride-n{n}", w, cact[p], ctok[p]))
+    return out
 
 
 def chain_rounds():

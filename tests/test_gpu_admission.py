@@ -105,6 +105,31 @@ def test_bucket_boundaries_vs_model(torch, k):
         eng.close()
 
 
+@pytest.mark.parametrize("n", A.CHUNK_N)
+def test_chunked_tile_scan_vs_closed_form(torch, n):
+    """1024, 1025 and 2049 tiles: the one-workgroup tile scan's threads own chunks of 1, 2 and 3 aggregates.  One bucket
+    that saturates many chunks behind its head, and a bucket head every 3000 positions; against the numpy closed form
+    (tests/test_admission_ref.py holds it to the model)."""
+    t = torch
+    for sc in A.chunk_scenarios(n):
+        eng = _engine(sc.n_act, max_batch=n)
+        try:
+            e_disp, e_state, e_counts = A.admit_closed_form(sc.act, sc.mflags, sc.state, sc.n_act, sc.hard, sc.hard_stateless)
+            d_state = _dev(t, sc.state)
+            disp, counts = _admit(t, eng, sc.n_act, sc.act, sc.mflags, d_state, sc.hard, sc.hard_stateless)
+            bad = np.nonzero(disp != e_disp)[0]
+            assert len(bad) == 0, (sc.name, len(bad), bad[:8], disp[bad[:8]], e_disp[bad[:8]])
+            state = d_state.cpu().numpy().view(A.STATE_DTYPE)
+            diff = np.nonzero(state != e_state)[0]
+            assert len(diff) == 0, (sc.name, len(diff), diff[:4], state[diff[:4]], e_state[diff[:4]])
+            assert list(counts) == list(e_counts), sc.name
+            if sc.n_act == 3:  # the saturation point lies behind the first chunk of every shape
+                sat = int(np.nonzero(e_disp == L.ADM_OVERLOADED)[0][0])
+                assert sat > 3 * 2048 and e_counts[L.ADM_RUN] > 0 and e_counts[L.ADM_ENQUEUE] > 0, (sc.name, sat)
+        finally:
+            eng.close()
+
+
 @pytest.mark.parametrize("build", [A.late_first_request_scenario, A.state_matrix_scenario, A.alias_scenario],
                          ids=["late-first-request", "state-matrix", "aliases"])
 def test_scenario_vs_model(torch, build):

@@ -134,6 +134,14 @@ def test_scan_density_vs_model(torch, n_act, density):
     _run(torch, R.density_scenario(n_act, density))
 
 
+@pytest.mark.parametrize("density", R.CHUNK_DENSITIES)
+@pytest.mark.parametrize("n_act", R.CHUNK_N_ACT)
+def test_chunked_tile_scan_vs_model(torch, n_act, density):
+    """The same at 1024, 1025 and 2049 tiles, where the threads of the one-workgroup tile scan own chunks of 1, 2 and 3
+    tile counts: one condemned activation per tile, and all of them."""
+    _run(torch, R.density_scenario(n_act, density))
+
+
 @pytest.mark.parametrize("build", [R.edge_scenario, R.matrix_scenario, R.quirk_scenario, R.branch_scenario, R.list_scenario],
                          ids=["tile-edges", "state-x-cflags", "scan-all-then-touch", "stale-branches", "lists"])
 def test_scenario_vs_model(torch, build):
@@ -230,6 +238,33 @@ def test_three_rounds_chained_on_one_stream_without_a_synchronise(torch):
     finally:
         eng.collector_destroy(col)
         eng.waitq_destroy(q)
+        eng.close()
+
+
+def test_create_has_finished_its_fills_before_the_first_call_on_the_stream(torch):
+    """orl_collector_create and orl_waitq_create zero-fill (and 0xFF-fill running_tok) on the null stream; the context's
+    stream does not wait for the null stream, so the create itself has to.  Eight times: create, write ticket[] /
+    running_tok through the view on the context's stream at once, read back."""
+    t = torch
+    n_act = 1 << 20
+    eng = _engine(n_act)
+    try:
+        src = t.arange(1, n_act + 1, dtype=t.int64, device="cuda")
+        exp = src.cpu().numpy()
+        t.cuda.synchronize()
+        for _ in range(8):
+            col = eng.collector_create(R.QUANTUM, R.T0)
+            eng.copy_on_device(eng.collector_view(col).d_ticket, src, 8 * n_act)
+            q = eng.waitq_create(1 << 20)
+            eng.copy_on_device(eng.waitq_view(q).d_running_tok, src, 4 * n_act)
+            eng.sync()
+            got = _host(eng, eng.collector_view(col).d_ticket, n_act, np.int64)
+            got_rt = _host(eng, eng.waitq_view(q).d_running_tok, n_act, np.uint32)
+            eng.collector_destroy(col)
+            eng.waitq_destroy(q)
+            assert np.array_equal(got, exp), np.nonzero(got != exp)[0][:8]
+            assert np.array_equal(got_rt, exp.view(np.uint32)[:n_act]), np.nonzero(got_rt != exp.view(np.uint32)[:n_act])[0][:8]
+    finally:
         eng.close()
 
 

@@ -256,6 +256,45 @@ def _append_raw(t, eng, q, n_act, act, tok, mflags, disp):
     eng.sync()
 
 
+@pytest.mark.parametrize("n", Q.CHUNK_N)
+def test_chunked_tile_scan_vs_closed_form(torch, n):
+    """1024, 1025 and 2049 tiles: the one-workgroup tile scan's threads own chunks of 1, 2 and 3 aggregates.  An append
+    of n positions into an empty store and a complete over a store of n records, each with everything in one bucket /
+    segment and with a head every 3000 positions; against the numpy forms (tests/test_completion_ref.py holds them to
+    the model)."""
+    t = torch
+    for (a_name, w0, act, tok, fl, disp), (c_name, w, cact, ctok) in zip(Q.chunk_appends(n), Q.chunk_completes(n)):
+        n_act = w.n_act
+        assert w0.n_act == n_act and len(act) == len(w.tok) == n
+        eng = _engine(n_act, max_batch=n)
+        q = eng.waitq_create(n)
+        try:
+            _load(t, eng, q, w0)
+            _append_raw(t, eng, q, n_act, act, tok, fl, disp)
+            Snapshot(eng, eng.waitq_view(q), n_act).check_store(Q.append_ref(w0, act, tok, fl, disp), a_name)
+            eng.waitq_destroy(q)
+            q = eng.waitq_create(n)
+            _load(t, eng, q, w)
+            e_w, e_out, e_counts = Q.complete_closed_form(w, cact, ctok, as_arrays=True)
+            d_state, d_cact, d_ctok = _dev(t, w.state), _dev(t, cact), _dev(t, ctok)
+            corder, coff = _bucket_arrays(t, len(cact), n_act)
+            counts = t.full((8,), -1, dtype=t.int64, device="cuda")
+            t.cuda.synchronize()
+            eng.bucket_device(d_cact, len(cact), corder, coff)
+            eng.complete_device(q, d_cact, d_ctok, len(cact), corder, coff, d_state, counts)
+            eng.sync()
+            s = Snapshot(eng, eng.waitq_view(q), n_act, d_state)
+            s.check_store(e_w, c_name)
+            assert s.out_n == len(e_out[0]) > 3 * 2048, (c_name, s.out_n, len(e_out[0]))
+            for col, (got, exp) in enumerate(zip(s.out, e_out)):
+                bad = np.nonzero(got != exp)[0]
+                assert len(bad) == 0, (c_name, "out column", col, len(bad), bad[:8], got[bad[:8]], exp[bad[:8]])
+            assert list(counts.cpu().numpy().view(np.uint64)) == list(e_counts), c_name
+        finally:
+            eng.waitq_destroy(q)
+            eng.close()
+
+
 def test_capacity_refresh_then_success_and_true_overflow(torch):
     """Capacity 100.  Batches of 60 messages with 10 ENQUEUEs each: after the first the library's bound says 60, so the
     second (60 + 60 > 100) asks the device (10) and goes through.  Then 20 records and a batch of 90: ORL_E_CAPACITY, and
