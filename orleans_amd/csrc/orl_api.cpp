@@ -1,5 +1,7 @@
 // orl_api.cpp — host side of liborleans_route.so: context, silo table + ring (membership events),
-// directory partition mirror (registration), identity hashes, and the C ABI entry points.
+// directory partition mirror (registration), identity hashes, and the context, directory and route entry points of the
+// C ABI.  The cache, stateless-worker, wire and scheduler entries are in api_cache / api_sw / api_wire / api_sched.cpp;
+// the context struct is in orl_ctx.h.
 //
 // The host side is the control plane of the path: everything here runs once per membership change or
 // registration, never per message.  Per-message work is in route_kernels.hip.
@@ -17,15 +19,8 @@
 #include <tuple>
 #include <vector>
 
-#include "orl_internal.h"
-#include "cache_adaptive.h"
-#include "admit.h"
-#include "waitq.h"
-#include "collect.h"
+#include "orl_ctx.h"
 #include "dir_versions.h"
-#include "cache_evict.h"
-
-using namespace orl;
 
 namespace {
 
@@ -180,168 +175,15 @@ int ensure_rank_mode(int device) {
     return 0;
 }
 
-// orl_route_batch: chunks per host-array batch (and the smallest chunk)
-constexpr size_t kHostChunks = 8;
-constexpr size_t kHostChunk = 1u << 20;
-
-uint64_t next_pow2(uint64_t v) {
-    uint64_t p = 16;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------------
-struct orl_ctx {
-    orl_config cfg{};
-    bool device_mode = false;
-    std::string err;
-    // silos (LocalGrainDirectory membership view)
-    uint32_t n_silos = 0;
-    std::vector<uint8_t> running, functional, local;
-    uint32_t seed = ORL_NULL_SILO;
-    std::vector<std::pair<int32_t, uint8_t>> ring;  // membershipRingList (signed hash, silo)
-    // directory partition mirror
-    std::vector<DirSlot> table;
-    uint64_t mask = 0, count = 0, tombs = 0;
-    bool dir_dirty = true;           // the whole table must be uploaded (and the probe tables rebuilt)
-    std::vector<uint32_t> dirty_slots;  // else: host-changed slots since the last upload, patched in place
-    std::vector<uint8_t> slot_marked;   // dirty_slots membership (one byte per slot, allocated on first use)
-    void* d_patch_data = nullptr;       // device staging of a slot patch (grows to the largest patch)
-    size_t patch_cap = 0;
-    uint64_t n_full_uploads = 0, n_patches = 0;
-    // follower graph of orl_csr_set (host-array fan-out)
-    uint64_t* d_csr_off = nullptr;
-    uint32_t* d_csr_tgt = nullptr;
-    size_t csr_nodes = 0;
-    std::vector<uint64_t> h_csr_off;
-    bool mirror_stale = false;       // device mutations since the mirror was last downloaded
-    uint64_t count_ub = 0, tombs_ub = 0;  // upper bounds while the mirror is stale (capacity checks without a sync)
-    // version tags (orl_dir_versions_enable; GrainInfo.VersionTag): one int32 per slot beside the mirror and beside the
-    // device table; they follow the slots through the upload, the slot patches, the mirror download and the compaction
-    bool versions = false;
-    std::vector<int32_t> vtag;
-    int32_t* d_vtag = nullptr;
-    // device state
-    DirSlot* d_table = nullptr;
-    ProbeSlot* d_probe = nullptr;    // compact probe table of d_table (ProbeSlot, orl_internal.h)
-    bool probe_valid = false;        // d_probe mirrors d_table (set by the host upload, cleared by device mutations)
-    bool probe_off = false;          // ORL_NO_PROBE16=1: always probe the 32-B table (A/B measurements)
-    bool probe_dev = false;          // d_probe was built on the device: validity in *d_probe_bad
-    uint2* d_probe8 = nullptr;       // 8-B form of the probe table (one type, 32-bit N1, 24-bit handles)
-    bool probe8_valid = false;       // d_probe8 mirrors d_table (host upload only)
-    bool probe8_off = false;         // ORL_NO_PROBE8=1: never the 8-B form (A/B measurements)
-    bool probe_dev_stale = false;    // device mutations since: rebuild before the next route launch
-    uint32_t* d_probe_bad = nullptr;
-    uint32_t* d_claim = nullptr;     // per-slot claim word of the device insert/remove kernels (0xFFFFFFFF at rest)
-    uint64_t* d_dirstate = nullptr;  // {entries, tombstones, error flag}
-    uint32_t* d_dslot = nullptr;     // per-message slot of a device directory batch
-    uint8_t* d_dflag = nullptr;      // per-message flag of a device cache batch
-    // KeyExt grains (round 5): host table + extension blob, uploaded whole when changed.  Round 6: registrations on the
-    // device (orl_dir_insert_keyext_device) make the device table the newer one (ext_dev_newer): the host functions first
-    // download it (ext_sync_host).  ext_dirty (host newer) and ext_dev_newer never hold together.
-    std::vector<ExtSlot> ext_table;
-    std::vector<uint8_t> ext_blob;
-    uint64_t ext_count = 0, ext_tombs = 0;
-    bool ext_dirty = false;
-    bool ext_dev_newer = false;
-    uint64_t ext_count_ub = 0, ext_tombs_ub = 0, ext_blob_ub = 0;  // upper bounds while the device is newer
-    uint64_t ext_blob_min_cap = 0;   // the device string store's capacity at the next upload (room for a device batch)
-    ExtSlot* d_ext_table = nullptr;
-    uint8_t* d_ext_blob = nullptr;
-    size_t d_ext_table_cap = 0, d_ext_blob_cap = 0;
-    uint32_t* d_ext_claim = nullptr;  // per-slot claim words of the device registration (0xFFFFFFFF at rest)
-    size_t d_ext_claim_cap = 0;
-    uint64_t* d_ext_state = nullptr;  // {string bytes used, entries, tombstones, error}
-    // directory cache (AdaptiveGrainDirectoryCache, f4): device table of remote-owned grains
-    DirSlot* d_cache = nullptr;
-    uint32_t* d_cclaim = nullptr;
-    uint64_t* d_cstate = nullptr;    // {entries, tombstones, error word, cumulative device evictions}
-    DirSlot* d_cache2 = nullptr;     // the second table a tombstone compaction rebuilds into (then the two swap)
-    CacheEvictScratch cev;           // scratch of the device eviction (cache_evict.hip), sized by orl_cache_config
-    uint32_t cache_mode = ORL_CACHE_EVICT_DEVICE;
-    uint64_t cache_host_evictions = 0, cache_evict_batches = 0, cache_rebuilds = 0, cache_host_fallbacks = 0;
-    uint64_t cache_slots = 0, cache_ub = 0, cache_tombs_ub = 0;
-    uint64_t cache_cap = 0;       // LRU.MaximumSize (orl_cache_config's capacity)
-    uint64_t cache_gen_free = 0;  // LRU.generationToFree: the generation of the last entry evicted
-    // adaptive mode (orl_cache_config_adaptive): both tables carry the per-slot state (orl_internal.h CacheAdaptive)
-    bool cache_adaptive = false;
-    int64_t cache_initial_ttl = 0, cache_max_ttl = 0;  // initialExpirationTimer, maxExpirationTimer (.NET ticks)
-    double cache_growth = 0;                           // exponentialTimerGrowth
-    int64_t cache_now = 0;                             // the last now_ticks a call gave (the plain add's DateTime.UtcNow)
-    AdmitScratch adm;                                  // orl_admit_device's scratch (admit.hip), allocated by its first call
-    CacheSweepScratch csw;                             // the maintainer's scratch and output (cache_adaptive.hip)
-    // stateless-worker grains (StatelessWorkerDirector.cs:35-80): the listed types with their MaxLocal, and the local
-    // catalog's host mirror (SwSlot), uploaded whole when the host changed it (sw_dirty).  orl_sw_set_busy_device makes
-    // the device table the newer one (sw_dev_newer): the host calls first read it back (sw_sync_host).  The two flags
-    // never hold together.
-    uint32_t sw_n = 0;
-    uint64_t sw_tcd[ORL_MAX_SW_TYPES] = {};
-    uint8_t sw_max[ORL_MAX_SW_TYPES] = {};
-    std::vector<SwSlot> sw_table;
-    uint64_t sw_mask = 0, sw_count = 0, sw_tombs = 0;
-    bool sw_dirty = false;
-    bool sw_dev_newer = false;
-    hipStream_t sw_dev_stream = nullptr;  // the stream of the last orl_sw_set_busy_device
-    SwSlot* d_sw = nullptr;
-    size_t d_sw_slots = 0;
-    RouteParams hp{};
-    RouteParams* d_params = nullptr;
-    bool params_dirty = true;
-    uint8_t* d_rank_of_silo = nullptr;
-    uint8_t h_rank_of_silo[256] = {};  // last uploaded rank_of_silo (uploads only on change: no per-batch sync)
-    bool ros_valid = false;
-    Scratch s{};
-    hipStream_t stream = nullptr;
-    // host-buffer staging (orl_route_batch / orl_hash_batch) and its copy streams / per-chunk events
-    uint8_t* st_in = nullptr; size_t st_in_cap = 0;
-    hipStream_t hstream[2] = {nullptr, nullptr};
-    hipEvent_t hev[2 * (kHostChunks + 1)] = {};
-    uint32_t* st_out = nullptr; size_t st_out_cap = 0;
-    uint32_t* st_off = nullptr;
-    // silo consistent hashes (SiloAddress.GetConsistentHashCode) for outbound sender queues
-    int32_t silo_hash[256] = {};
-    uint8_t silo_known[256] = {};
-    bool silo_hash_dirty = true;
-    int32_t* d_silo_hash = nullptr;
-    uint8_t* d_silo_known = nullptr;
-    // stream / reminder virtual-bucket ring (VirtualBucketsRingProvider.bucketsMap)
-    uint32_t vr_nb = 30;
-    std::map<uint32_t, uint8_t> vr_map;                // bucket hash → silo
-    std::map<uint8_t, std::vector<uint32_t>> vr_hashes;  // silo → its GetUniformHashCodes
-    std::map<uint8_t, int32_t> vr_gen;
-    bool vr_dirty = false;
-    uint32_t vr_n_dev = 0;
-    uint32_t* d_vr_hash = nullptr;
-    uint8_t* d_vr_silo = nullptr;
-    // f2: serialized SiloAddress -> silo index for the wire decoder
-    uint32_t silo_addr[256][6] = {};
-    uint8_t silo_addr_known[256] = {};
-    bool silo_addr_dirty = true;
-    SiloAddrEntry* d_silo_tab = nullptr;
-    uint32_t* d_decode_flag = nullptr;
-    uint32_t* d_silo_words = nullptr;  // [256][6] serialized SiloAddress by silo index (stamp)
-    // f2 emit: grain class names by type code, and the stamp's scratch
-    std::map<int32_t, std::string> grain_types;
-    bool gt_dirty = true;
-    GrainTypeEntry* d_gt = nullptr;
-    uint8_t* d_gt_blob = nullptr;
-    uint64_t* d_stamp_sizes = nullptr;
-    void* d_stamp_temp = nullptr;
-    size_t stamp_cap = 0, stamp_temp_bytes = 0;
-    // timing: 4 events per recorded batch (call begin, route begin, route end, call end)
-    bool timing = false;
-    std::vector<hipEvent_t> tev;
-    uint32_t tcount = 0;
-};
 
 const uint64_t* orl::ctx_wire_tcd(const orl_ctx* c) {
     if (!c || !c->d_params) return nullptr;
     return reinterpret_cast<const uint64_t*>(reinterpret_cast<const uint8_t*>(c->d_params) + offsetof(RouteParams, wire_tcd));
 }
 
-namespace {
+namespace orl {
+namespace host {
 
 int fail(orl_ctx* c, int code, const char* fmt, ...) {
     if (c) {
@@ -359,11 +201,10 @@ int hipfail(orl_ctx* c, hipError_t e, const char* what) {
     return fail(c, ORL_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
 }
 
-#define ORL_HIP(c, call)                                           \
-    do {                                                           \
-        hipError_t _e = (call);                                    \
-        if (_e != hipSuccess) return hipfail((c), _e, #call);      \
-    } while (0)
+}  // namespace host
+}  // namespace orl
+
+namespace {
 
 bool silo_ok(const orl_ctx* c, uint32_t s) { return s < c->n_silos; }
 
@@ -589,8 +430,13 @@ bool state_dirty(const orl_ctx* c) {
            !c->dirty_slots.empty() || c->sw_dirty;
 }
 
+}  // namespace
+
+namespace orl {
+namespace host {
+
 int sync_device_state(orl_ctx* c) {
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (!state_dirty(c)) return ORL_OK;
     // A batch launched earlier on any stream may still be reading the tables and params below: wait for the device
     // before overwriting them, so membership / registration changes take effect between batches.
@@ -682,6 +528,11 @@ int sync_device_state(orl_ctx* c) {
     return ORL_OK;
 }
 
+}  // namespace host
+}  // namespace orl
+
+namespace {
+
 // The SW kernel forms' argument: the listed types and the device catalog (n = 0: no types set, the plain forms run).
 SwView sw_view(const orl_ctx* c) {
     SwView v{};
@@ -712,13 +563,6 @@ int prepare_probe(orl_ctx* c, hipStream_t st) {
     c->probe_dev_stale = false;
     c->probe_dev = true;
     return ORL_OK;
-}
-
-void set_cache_on(orl_ctx* c, bool on) {
-    if (c->hp.cache_on != (on ? 1u : 0u)) {
-        c->hp.cache_on = on ? 1u : 0u;
-        c->params_dirty = true;
-    }
 }
 
 // Exact device-table counters after device mutations (synchronises the device; 24 bytes, no table download).
@@ -1067,20 +911,18 @@ uint32_t orl_keyext_uniform_hash(const orl_grain_key* k, const char* ext, size_t
     return jenkins_bytes(b.data(), b.size());
 }
 
-}  // extern "C"
-namespace {
 // ---- KeyExt grains (round 5): the host table, first writer wins, tombstones, rebuilt (and the blob compacted) when full
-uint32_t keyext_hash(const orl_grain_key& k, const uint8_t* ext, uint32_t len) {
+static uint32_t keyext_hash(const orl_grain_key& k, const uint8_t* ext, uint32_t len) {
     return orl_keyext_uniform_hash(&k, reinterpret_cast<const char*>(ext), len);
 }
 
-bool ext_equal(const orl_ctx* c, const ExtSlot& e, const orl_grain_key& k, uint32_t h, const uint8_t* ext, uint32_t len) {
+static bool ext_equal(const orl_ctx* c, const ExtSlot& e, const orl_grain_key& k, uint32_t h, const uint8_t* ext, uint32_t len) {
     return e.state == SLOT_FULL && e.hash == h && e.tcd == k.type_code_data && e.n0 == k.n0 && e.n1 == k.n1 && e.len == len &&
            (len == 0 || std::memcmp(c->ext_blob.data() + e.off, ext, len) == 0);
 }
 
 // Slot of the key (or -1); *free_slot = the first tombstone / empty slot of its chain.
-int64_t ext_find(const orl_ctx* c, const orl_grain_key& k, uint32_t h, const uint8_t* ext, uint32_t len, int64_t* free_slot) {
+static int64_t ext_find(const orl_ctx* c, const orl_grain_key& k, uint32_t h, const uint8_t* ext, uint32_t len, int64_t* free_slot) {
     if (free_slot) *free_slot = -1;
     if (c->ext_table.empty()) return -1;
     const uint64_t mask = c->ext_table.size() - 1;
@@ -1101,7 +943,7 @@ int64_t ext_find(const orl_ctx* c, const orl_grain_key& k, uint32_t h, const uin
 }
 
 // Rebuild with room for `need` entries at load <= 1/2, without tombstones, the blob compacted.
-void ext_rebuild(orl_ctx* c, uint64_t need) {
+static void ext_rebuild(orl_ctx* c, uint64_t need) {
     uint64_t size = 1024;
     while (size < 2 * need) size <<= 1;
     std::vector<ExtSlot> old;
@@ -1124,7 +966,7 @@ void ext_rebuild(orl_ctx* c, uint64_t need) {
 }
 
 // The ring owner of a KeyExt hash (CalculateTargetSilo :466-494), as host_owner computes it for the u64 path.
-uint32_t host_owner_hash(const orl_ctx* c, int32_t h, uint32_t me, bool excl) {
+static uint32_t host_owner_hash(const orl_ctx* c, int32_t h, uint32_t me, bool excl) {
     const bool running = me < c->n_silos && c->running[me];
     const int n = (int)c->ring.size();
     if (n == 0) return (excl && !running) ? ORL_NULL_SILO : me;
@@ -1142,7 +984,7 @@ uint32_t host_owner_hash(const orl_ctx* c, int32_t h, uint32_t me, bool excl) {
 }
 
 // Every reference of a host KeyExt call inside the caller's blob (the entry points used to read past it).
-int check_ext_refs(orl_ctx* c, const orl_ext_ref* ext, size_t n, uint64_t blob_bytes) {
+static int check_ext_refs(orl_ctx* c, const orl_ext_ref* ext, size_t n, uint64_t blob_bytes) {
     for (size_t i = 0; i < n; ++i)
         if ((uint64_t)ext[i].off + ext[i].len > blob_bytes)
             return fail(c, ORL_E_INVALID, "KeyExt reference %zu (%u + %u bytes) outside the %llu-byte blob", i, ext[i].off,
@@ -1151,7 +993,7 @@ int check_ext_refs(orl_ctx* c, const orl_ext_ref* ext, size_t n, uint64_t blob_b
 }
 
 // The host mirror after device registrations: the table, the used string store and the exact counters (synchronises).
-int ext_sync_host(orl_ctx* c) {
+static int ext_sync_host(orl_ctx* c) {
     if (!c->ext_dev_newer) return ORL_OK;
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     ORL_HIP(c, hipDeviceSynchronize());
@@ -1173,7 +1015,7 @@ int ext_sync_host(orl_ctx* c) {
     return ORL_OK;
 }
 
-int upload_keyext(orl_ctx* c) {
+static int upload_keyext(orl_ctx* c) {
     if (!c->ext_dirty) return ORL_OK;
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     ORL_HIP(c, hipDeviceSynchronize());  // batches in flight may read the old table (snapshot semantics, as the partition)
@@ -1211,8 +1053,6 @@ int upload_keyext(orl_ctx* c) {
     c->ext_dirty = false;
     return ORL_OK;
 }
-}  // namespace
-extern "C" {
 
 int orl_dir_insert_keyext(orl_ctx* c, const orl_grain_key* keys, const orl_ext_ref* ext, const uint8_t* blob,
                           uint64_t blob_bytes, const uint32_t* acts, const uint8_t* silos, size_t n, uint32_t* wact,
@@ -1316,7 +1156,7 @@ int orl_dir_insert_keyext_device(orl_ctx* c, const orl_grain_key* d_keys, const 
     if (!c) return ORL_E_INVALID;
     if (!c->device_mode) return fail(c, ORL_E_STATE, "no device");
     if (n && (!d_keys || !d_ext || !d_blob || !d_acts || !d_silos || !d_status)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (int r = check_batch(c, n)) return r;
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     if (blob_bytes > UINT32_MAX) return fail(c, ORL_E_INVALID, "KeyExt blob of %llu bytes (<= 4 GiB)", (unsigned long long)blob_bytes);
     if (n == 0) return ORL_OK;
@@ -1344,7 +1184,7 @@ int orl_dir_insert_keyext_device(orl_ctx* c, const orl_grain_key* d_keys, const 
         if ((r = upload_keyext(c))) return r;
         if (!fits()) return fail(c, ORL_E_CAPACITY, "KeyExt table: no room for a batch of %zu", n);
     }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int e = launch_keyext_insert(c->d_params, c->d_ext_table, c->ext_table.size() - 1, c->d_ext_claim, c->d_ext_blob,
                                  c->d_ext_blob_cap, d_keys, d_ext, d_blob, blob_bytes, d_acts, d_silos, n, c->cfg.n_act,
                                  c->n_silos, c->d_dslot, d_wact, d_wsilo, d_status, c->d_ext_state, st);
@@ -1355,14 +1195,10 @@ int orl_dir_insert_keyext_device(orl_ctx* c, const orl_grain_key* d_keys, const 
     return ORL_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
 // orl_dir_insert_single and its versioned form: tags == nullptr is the unversioned call (every draw 0 on a versioned
 // partition); wtag is written only by the versioned call.
-int dir_insert_host(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const int32_t* tags,
-                    size_t n, uint32_t* wact, uint8_t* wsilo, int32_t* wtag, uint8_t* status) {
+static int dir_insert_host(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const int32_t* tags,
+                           size_t n, uint32_t* wact, uint8_t* wsilo, int32_t* wtag, uint8_t* status) {
     if (int r = ensure_mirror(c)) return r;
     for (size_t i = 0; i < n; ++i) {
         uint8_t st;
@@ -1412,14 +1248,11 @@ int dir_insert_host(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts,
     return ORL_OK;
 }
 
-int need_versions(orl_ctx* c, bool device = false) {
-    if (device && !c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+static int need_versions(orl_ctx* c, bool device = false) {
+    if (device)
+        if (int r = need_device(c)) return r;
     return c->versions ? ORL_OK : fail(c, ORL_E_STATE, "version tags are not enabled (orl_dir_versions_enable)");
 }
-
-}  // namespace
-
-extern "C" {
 
 int orl_dir_insert_single(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n,
                           uint32_t* wact, uint8_t* wsilo, uint8_t* status) {
@@ -1532,7 +1365,7 @@ int orl_dir_lookup_host(const orl_ctx* c, const orl_grain_key* keys, size_t n, u
 
 int orl_hash_batch(orl_ctx* c, const orl_grain_key* keys, size_t n, uint32_t* out) {
     if (!c || (n && (!keys || !out))) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (n == 0) return ORL_OK;
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     int r = ensure_staging(c, n * sizeof(orl_grain_key), n);
@@ -1545,19 +1378,18 @@ int orl_hash_batch(orl_ctx* c, const orl_grain_key* keys, size_t n, uint32_t* ou
     return ORL_OK;
 }
 
-namespace {
-int route_impl(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, uint32_t* d_route, uint32_t* d_act,
-               uint32_t* d_order, uint32_t* d_off, void* stream, const uint32_t* d_in_act = nullptr) {
+static int route_impl(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, uint32_t* d_route, uint32_t* d_act,
+                      uint32_t* d_order, uint32_t* d_off, void* stream, const uint32_t* d_in_act = nullptr) {
     if (!c) return ORL_E_INVALID;
     if (fmt != 8 && fmt != 16 && fmt != 32) return fail(c, ORL_E_INVALID, "record width %d (8, 16 or 32)", fmt);
     if (n && (!d_in || !d_route || !d_act)) return fail(c, ORL_E_INVALID, "null device buffer");
     const bool buckets = !(opts & ORL_OPT_NO_BUCKETS);
     if (buckets && (!d_off || (n && !d_order))) return fail(c, ORL_E_INVALID, "null order/offsets buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (int r = check_batch(c, n)) return r;
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
     if (r) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     hipEvent_t* ev = nullptr;
     if (c->timing && n > 0 && c->tcount < ORL_TIMING_SLOTS) ev = &c->tev[4 * (size_t)c->tcount++];
     if ((r = prepare_probe(c, st))) return r;
@@ -1571,34 +1403,6 @@ int route_impl(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, u
     if (ev) ORL_HIP(c, hipEventRecord(ev[3], st));
     return ORL_OK;
 }
-}  // namespace
-
-}  // extern "C"
-namespace orl {
-int ctx_route_received(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, uint32_t* d_route, uint32_t* d_act,
-                       const uint32_t* d_in_act, void* stream) {
-    return route_impl(c, d_in, fmt, n, opts | ORL_OPT_NO_BUCKETS, d_route, d_act, nullptr, nullptr, stream, d_in_act);
-}
-
-bool ctx_cache_on(orl_ctx* c) { return c && c->d_cache && c->hp.cache_on; }
-
-bool ctx_sw_on(const orl_ctx* c) { return c && c->sw_n != 0; }
-
-int ctx_keyext_prepare(orl_ctx* c) { return upload_keyext(c); }
-
-int ctx_route_keyext_received(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const orl_ext_ref* d_ext,
-                              const uint8_t* d_blob, uint64_t blob_bytes, uint32_t* d_route, uint32_t* d_act, void* stream) {
-    if (n == 0) return ORL_OK;
-    const uint32_t excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) ? 1u : 0u;
-    int e = launch_keyext_route(c->d_params, d_in, n, d_ext, d_blob, blob_bytes, c->d_ext_table,
-                                c->ext_table.empty() ? 0 : c->ext_table.size() - 1, c->d_ext_blob, excl, d_route, d_act,
-                                stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "KeyExt route launch (node)");
-    return ORL_OK;
-}
-const uint32_t* ctx_stage4_err(const orl_ctx* c) { return c->s.s4_err; }
-}  // namespace orl
-extern "C" {
 
 int orl_route_batch_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, uint32_t* d_route, uint32_t* d_act,
                            uint32_t* d_order, uint32_t* d_off, void* stream) {
@@ -1628,7 +1432,7 @@ int orl_route_keyext_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint3
     if (buckets && (!d_off || (n && !d_order))) return fail(c, ORL_E_INVALID, "null order/offsets buffer");
     if (int r = upload_keyext(c)) return r;
     if (int r = route_impl(c, d_in, 32, n, opts | ORL_OPT_NO_BUCKETS, d_route, d_act, nullptr, nullptr, stream)) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (n) {
         const uint32_t excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) ? 1u : 0u;
         int e = launch_keyext_route(c->d_params, d_in, n, d_ext, d_blob, blob_bytes, c->d_ext_table,
@@ -1646,15 +1450,14 @@ int orl_route_keyext_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint3
 // neighbouring chunks', and stage 4 runs once over the whole batch at the end.  Caller arrays registered with
 // orl_host_register (pinned) are copied asynchronously at full PCIe rate; pageable ones go through the runtime's
 // staging (correct, slower).  fmt = the input record width (32 = orl_msg_hdr, 8 = orl_wire8).
-namespace {
-int route_batch_host(orl_ctx* c, const void* in, int fmt, size_t n, uint32_t opts, uint32_t* route, uint32_t* act,
-                     uint32_t* order, uint32_t* offsets) {
+static int route_batch_host(orl_ctx* c, const void* in, int fmt, size_t n, uint32_t opts, uint32_t* route, uint32_t* act,
+                            uint32_t* order, uint32_t* offsets) {
     if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     const bool buckets = !(opts & ORL_OPT_NO_BUCKETS);
     if (n && (!in || !route || !act)) return fail(c, ORL_E_INVALID, "null host buffer");
     if (buckets && (!offsets || (n && !order))) return fail(c, ORL_E_INVALID, "null order/offsets buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (int r = check_batch(c, n)) return r;
     if (fmt == 8 && c->hp.n_wire_types == 0) return fail(c, ORL_E_STATE, "8-byte records need the wire types (orl_wire_types_set)");
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     int r = ensure_staging(c, std::max<size_t>(n, 1) * sizeof(orl_msg_hdr), std::max<size_t>(n, 1) * 3);
@@ -1696,7 +1499,6 @@ int route_batch_host(orl_ctx* c, const void* in, int fmt, size_t n, uint32_t opt
     ORL_HIP(c, hipStreamSynchronize(up));
     return ORL_OK;
 }
-}  // namespace
 
 int orl_route_batch(orl_ctx* c, const orl_msg_hdr* in, size_t n, uint32_t opts, uint32_t* route, uint32_t* act,
                     uint32_t* order, uint32_t* offsets) {
@@ -1708,11 +1510,10 @@ int orl_route_batch_narrow(orl_ctx* c, const orl_wire8* in, size_t n, uint32_t o
     return route_batch_host(c, in, 8, n, opts, route, act, order, offsets);
 }
 
-namespace {
-int fanout_impl(orl_ctx* c, const orl_msg_hdr* d_direct, size_t n_direct, const uint64_t* d_csr_off, const uint32_t* d_csr_tgt,
-                const orl_grain_key* d_keys, const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub,
-                uint64_t follower_tcd, uint32_t opts, uint64_t* d_pub_offsets, uint32_t* d_route, uint32_t* d_act,
-                uint32_t* d_order, uint32_t* d_off, uint64_t* n_out, void* stream) {
+static int fanout_impl(orl_ctx* c, const orl_msg_hdr* d_direct, size_t n_direct, const uint64_t* d_csr_off, const uint32_t* d_csr_tgt,
+                       const orl_grain_key* d_keys, const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub,
+                       uint64_t follower_tcd, uint32_t opts, uint64_t* d_pub_offsets, uint32_t* d_route, uint32_t* d_act,
+                       uint32_t* d_order, uint32_t* d_off, uint64_t* n_out, void* stream) {
     if (!c || !n_out) return ORL_E_INVALID;
     // k_fanout_route has no stateless-worker form.  The follower-type form can tell from its one type that no emitted
     // message is of a listed type; the key-table and mixed forms cannot, and refuse while types are set (expand + route
@@ -1737,7 +1538,7 @@ int fanout_impl(orl_ctx* c, const orl_msg_hdr* d_direct, size_t n_direct, const 
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
     if (r) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     hipEvent_t* ev = nullptr;
     if (c->timing && c->tcount < ORL_TIMING_SLOTS) ev = &c->tev[4 * (size_t)c->tcount++];
     if ((r = prepare_probe(c, st))) return r;
@@ -1758,7 +1559,6 @@ int fanout_impl(orl_ctx* c, const orl_msg_hdr* d_direct, size_t n_direct, const 
     }
     return ORL_OK;
 }
-}  // namespace
 
 int orl_fanout_route_device(orl_ctx* c, const uint64_t* d_csr_off, const uint32_t* d_csr_tgt, const uint32_t* d_pubs,
                             const uint8_t* d_pub_silo, size_t n_pub, uint64_t follower_tcd, uint32_t opts,
@@ -1796,14 +1596,14 @@ int orl_fanout_expand_device(orl_ctx* c, const uint64_t* d_csr_off, const uint32
                              uint64_t follower_tcd, const uint32_t* d_pubs, const uint8_t* d_pub_silo, size_t n_pub, uint32_t opts,
                              uint64_t* d_pub_offsets, orl_msg_hdr* d_out, uint64_t cap, uint64_t* n_out, void* stream) {
     if (!c || !n_out) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (!d_csr_off || !d_csr_tgt || !d_pub_offsets || (cap && !d_out)) return fail(c, ORL_E_INVALID, "null device buffer");
     if (n_pub && (!d_pubs || !d_pub_silo)) return fail(c, ORL_E_INVALID, "null publisher buffer");
     if (n_pub + 1 > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "too many publishers");
     if ((opts & ORL_OPT_TOTAL_GIVEN) && *n_out > cap)
         return fail(c, ORL_E_CAPACITY, "given fan-out total %llu > cap %llu", (unsigned long long)*n_out, (unsigned long long)cap);
     ORL_HIP(c, hipSetDevice(c->cfg.device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const int e = launch_fanout_expand(d_csr_off, d_csr_tgt, d_keys, d_pubs, d_pub_silo, n_pub, d_keys ? 0 : follower_tcd, opts,
                                        d_pub_offsets, d_out, n_out, cap, c->s, st);
     if (e == -1) return fail(c, ORL_E_CAPACITY, "fan-out emits %llu > cap %llu", (unsigned long long)*n_out, (unsigned long long)cap);
@@ -1811,10 +1611,9 @@ int orl_fanout_expand_device(orl_ctx* c, const uint64_t* d_csr_off, const uint32
     return ORL_OK;
 }
 
-namespace {
 // Shared checks of the two partition entry points + the rank_of_silo upload (only when it changes).
-int partition_prologue(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, const uint8_t* rank_of_silo, uint32_t nranks,
-                       uint32_t my_rank, const void* d_out, uint64_t* d_counts, hipStream_t st) {
+static int partition_prologue(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, const uint8_t* rank_of_silo, uint32_t nranks,
+                              uint32_t my_rank, const void* d_out, uint64_t* d_counts, hipStream_t st) {
     if (nranks == 0 || nranks > 8 || my_rank >= nranks) return fail(c, ORL_E_INVALID, "nranks must be 1..8 and my_rank < nranks");
     if (n && (!d_in || !d_out)) return fail(c, ORL_E_INVALID, "null device buffer");
     if (!d_counts) return fail(c, ORL_E_INVALID, "null counts buffer");
@@ -1835,14 +1634,13 @@ int partition_prologue(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, const uint
     }
     return ORL_OK;
 }
-}  // namespace
 
 int orl_partition_by_owner_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const uint8_t* rank_of_silo,
                                   uint32_t nranks, uint32_t my_rank, orl_msg_hdr* d_out, uint32_t* d_src, uint64_t* d_counts,
                                   void* stream) {
     if (!c || !rank_of_silo) return ORL_E_INVALID;
     if (n && !d_src) return fail(c, ORL_E_INVALID, "null device buffer");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
     const SwView swv = sw_view(c);
@@ -1857,7 +1655,7 @@ int orl_partition_by_owner_padded_device(orl_ctx* c, const orl_msg_hdr* d_in, si
                                          orl_msg_hdr* d_out, uint32_t* d_src, uint64_t* d_counts, void* stream) {
     if (!c || !rank_of_silo) return ORL_E_INVALID;
     if (stride < n) return fail(c, ORL_E_INVALID, "stride %zu < batch %zu", stride, n);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
     const SwView swv = sw_view(c);
@@ -1867,38 +1665,13 @@ int orl_partition_by_owner_padded_device(orl_ctx* c, const orl_msg_hdr* d_in, si
     return ORL_OK;
 }
 
-}  // extern "C"
-namespace orl {
-// The node's hop-1 partition: any record width, with the status word (look-back failures included) for every width.
-int ctx_partition_padded(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const uint8_t* rank_of_silo,
-                         uint32_t nranks, uint32_t my_rank, size_t stride, void* d_out, int fmt, uint64_t* d_counts,
-                         uint32_t* d_status, void* stream, uint32_t* d_act_out, const KxLanes* kxl) {
-    if (!c || !rank_of_silo || !d_status) return ORL_E_INVALID;
-    if (fmt != 8 && fmt != 16 && fmt != 32) return fail(c, ORL_E_INVALID, "record width %d", fmt);
-    if (stride < n) return fail(c, ORL_E_INVALID, "stride %zu < batch %zu", stride, n);
-    if (fmt == 8 && c->hp.n_wire_types == 0) return fail(c, ORL_E_STATE, "8-byte records need the wire types (orl_wire_types_set)");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
-    if (r) return r;
-    const bool cached = d_act_out && ctx_cache_on(c);
-    const SwView swv = sw_view(c);
-    int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, fmt, nullptr,
-                                    d_counts, d_status, c->s, st, cached ? c->d_cache : nullptr,
-                                    cached ? c->cache_slots - 1 : 0, cached ? d_act_out : nullptr, kxl, swv.n ? &swv : nullptr);
-    if (!e && cached) e = launch_cache_gen_advance(c->d_cache, c->cache_slots - 1, n, st);  // the sender's lookups' LRU stamps
-    if (e) return hipfail(c, (hipError_t)e, "node partition launch");
-    return ORL_OK;
-}
-}  // namespace orl
-extern "C" {
-
 int orl_partition_compact_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const uint8_t* rank_of_silo,
                                  uint32_t nranks, uint32_t my_rank, size_t stride, orl_wire_msg* d_out, uint32_t* d_src,
                                  uint64_t* d_counts, uint32_t* d_status, void* stream) {
     if (!c || !rank_of_silo) return ORL_E_INVALID;
     if (stride < n) return fail(c, ORL_E_INVALID, "stride %zu < batch %zu", stride, n);
     if (!d_status) return fail(c, ORL_E_INVALID, "null status word");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
     const SwView swv = sw_view(c);
@@ -1915,7 +1688,7 @@ int orl_partition_narrow_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, u
     if (stride < n) return fail(c, ORL_E_INVALID, "stride %zu < batch %zu", stride, n);
     if (!d_status) return fail(c, ORL_E_INVALID, "null status word");
     if (c->hp.n_wire_types == 0) return fail(c, ORL_E_STATE, "8-byte records need the wire types (orl_wire_types_set)");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
     if (r) return r;
     const SwView swv = sw_view(c);
@@ -1931,7 +1704,7 @@ int orl_partition_cached_device(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, u
     if (!c || !rank_of_silo) return ORL_E_INVALID;
     if (n && !d_act_out) return fail(c, ORL_E_INVALID, "null act lane");
     if (!ctx_cache_on(c) && n) {  // no cache: every record unaddressed
-        hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+        hipStream_t st = stream_of(c, stream);
         for (uint32_t r = 0; r < nranks && r < 8; ++r)
             ORL_HIP(c, hipMemsetAsync(d_act_out + (size_t)r * stride, 0xFF, n * 4, st));
     }
@@ -1944,34 +1717,9 @@ int orl_route_received_device(orl_ctx* c, const void* d_in, uint32_t fmt, size_t
     return ctx_route_received(c, d_in, (int)fmt, n, opts, d_route, d_act, d_in_act, stream);
 }
 
-int orl_wire_types_set(orl_ctx* c, uint32_t n, const uint64_t* tcd) {
-    if (!c) return ORL_E_INVALID;
-    if (n > ORL_MAX_WIRE_TYPES || (n && !tcd)) return fail(c, ORL_E_INVALID, "wire types: n = %u (at most %u)", n, ORL_MAX_WIRE_TYPES);
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t j = 0; j < i; ++j)
-            if (tcd[i] == tcd[j]) return fail(c, ORL_E_INVALID, "wire types: entry %u repeats entry %u", i, j);
-    RouteParams& P = c->hp;
-    std::memset(P.wire_tcd, 0, sizeof P.wire_tcd);
-    if (n) std::memcpy(P.wire_tcd, tcd, n * sizeof(uint64_t));
-    P.n_wire_types = n;
-    uint64_t h = 0xCBF29CE484222325ull;  // FNV-1a over the count and the values, little-endian bytes
-    auto mix = [&](uint64_t v) {
-        for (int b = 0; b < 8; ++b) { h ^= (v >> (8 * b)) & 0xFFu; h *= 0x100000001B3ull; }
-    };
-    mix(n);
-    for (uint32_t i = 0; i < n; ++i) mix(tcd[i]);
-    P.wire_digest = n ? h : 0;
-    c->params_dirty = true;
-    return ORL_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
 // The tags a device registration or merge kernel sees: none on a partition without versions; d_in / d_draws == nullptr
 // are the unversioned calls on a versioned partition (zeros).
-DirTags dir_tags(const orl_ctx* c, const int32_t* d_in, const int32_t* d_draws, int32_t* d_winner) {
+static DirTags dir_tags(const orl_ctx* c, const int32_t* d_in, const int32_t* d_draws, int32_t* d_winner) {
     DirTags vt;
     if (c->versions) {
         vt.slot = c->d_vtag;
@@ -1982,10 +1730,10 @@ DirTags dir_tags(const orl_ctx* c, const int32_t* d_in, const int32_t* d_draws, 
     return vt;
 }
 
-int dir_insert_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                      const int32_t* d_tags, size_t n, uint32_t* d_wact, uint8_t* d_wsilo, int32_t* d_wtag, uint8_t* d_status,
-                      void* stream) {
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+static int dir_insert_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                             const int32_t* d_tags, size_t n, uint32_t* d_wact, uint8_t* d_wsilo, int32_t* d_wtag, uint8_t* d_status,
+                             void* stream) {
+    if (int r = check_batch(c, n)) return r;
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
     if (r) return r;
@@ -1999,7 +1747,7 @@ int dir_insert_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d
             return fail(c, ORL_E_CAPACITY, "directory full (%llu entries + %llu tombstones + batch %zu; orl_dir_compact "
                         "drops tombstones)", (unsigned long long)c->count_ub, (unsigned long long)c->tombs_ub, n);
     }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int e = launch_dir_insert(c->d_params, c->d_table, c->mask, c->d_claim, c->d_dirstate, d_keys, d_acts, d_silos, n,
                               c->cfg.n_act, c->n_silos, c->d_dslot, d_wact, d_wsilo, d_status,
                               reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st, dir_tags(c, d_tags, nullptr, d_wtag));
@@ -2010,10 +1758,10 @@ int dir_insert_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d
     return ORL_OK;
 }
 
-int dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                     const int32_t* d_tags, const int32_t* d_draws, size_t n, const orl_grain_key* d_act_keys,
-                     uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act, uint8_t* d_dropped_silo, void* stream) {
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+static int dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
+                            const int32_t* d_tags, const int32_t* d_draws, size_t n, const orl_grain_key* d_act_keys,
+                            uint32_t n_act_keys, uint8_t* d_status, uint32_t* d_dropped_act, uint8_t* d_dropped_silo, void* stream) {
+    if (int r = check_batch(c, n)) return r;
     if (c->n_silos == 0) return fail(c, ORL_E_STATE, "silo table not set");
     int r = sync_device_state(c);
     if (r) return r;
@@ -2026,7 +1774,7 @@ int dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_
             return fail(c, ORL_E_CAPACITY, "directory full (%llu entries + %llu tombstones + batch %zu)",
                         (unsigned long long)c->count_ub, (unsigned long long)c->tombs_ub, n);
     }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int e = launch_dir_merge(c->d_table, c->mask, c->d_claim, c->d_dirstate, d_keys, d_acts, d_silos, n, c->cfg.n_act, c->n_silos,
                              d_act_keys, n_act_keys, c->d_dslot, d_status, d_dropped_act, d_dropped_silo,
                              reinterpret_cast<uint32_t*>(c->d_dirstate + 2), st, dir_tags(c, d_tags, d_draws, nullptr));
@@ -2036,10 +1784,6 @@ int dir_merge_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_
     probe_after_device_mutation(c);
     return ORL_OK;
 }
-
-}  // namespace
-
-extern "C" {
 
 int orl_dir_insert_single_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
                                  size_t n, uint32_t* d_wact, uint8_t* d_wsilo, uint8_t* d_status, void* stream) {
@@ -2085,7 +1829,7 @@ int orl_dir_lookup_many_device(orl_ctx* c, const orl_grain_key* d_keys, const in
     if (n && (!d_keys || !d_etags || !d_kind || !d_etag_out || !d_act || !d_silo)) return fail(c, ORL_E_INVALID, "null device buffer");
     int r = sync_device_state(c);  // ORL_E_STATE on a host-only context; host-side changes go up first
     if (r) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int e = launch_lookup_many(c->d_params, c->d_table, c->mask, c->d_vtag, d_keys, d_etags, n, d_kind, d_etag_out, d_act, d_silo,
                                d_counts, st);
     if (e) return hipfail(c, (hipError_t)e, "lookup-many launch");
@@ -2095,10 +1839,10 @@ int orl_dir_lookup_many_device(orl_ctx* c, const orl_grain_key* d_keys, const in
 int orl_dir_remove_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, uint8_t* d_removed, void* stream) {
     if (!c) return ORL_E_INVALID;
     if (n && (!d_keys || !d_removed)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
+    if (int r = check_batch(c, n)) return r;
     int r = sync_device_state(c);
     if (r) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     int e = launch_dir_remove(c->d_table, c->mask, c->d_claim, c->d_dirstate, d_keys, n, c->d_dslot, d_removed, st);
     if (e) return hipfail(c, (hipError_t)e, "directory remove launch");
     c->tombs_ub += n;
@@ -2117,7 +1861,7 @@ int orl_dir_split_device(orl_ctx* c, uint32_t me, uint32_t flags, orl_grain_key*
     // the tile counts live in the scratch histogram: a table of more slots than the scan scratch is split by the host
     if ((c->table.size() + kTile - 1) / kTile > c->s.max_tiles * (1ull << kMaxDigitBits))
         return fail(c, ORL_E_CAPACITY, "table too large for the split scratch");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const bool remove = flags & ORL_SPLIT_REMOVE;
     int e = launch_dir_split(c->d_params, c->d_table, c->table.size(), me, remove, c->d_dirstate, d_keys, d_acts, d_silos, cap,
                              d_n_out, c->s, st);
@@ -2217,14 +1961,12 @@ int orl_vring_get(const orl_ctx* c, uint32_t* hashes, uint8_t* silos, uint32_t c
     return ORL_OK;
 }
 
-namespace {
-int ring_prologue(orl_ctx* c, uint32_t kind, uint32_t me, uint32_t opts, bool* excl) {
+static int ring_prologue(orl_ctx* c, uint32_t kind, uint32_t me, uint32_t opts, bool* excl) {
     if (kind != ORL_RING_CONSISTENT && kind != ORL_RING_VBUCKETS) return fail(c, ORL_E_INVALID, "unknown ring kind %u", kind);
     if (!silo_ok(c, me)) return fail(c, ORL_E_INVALID, "silo %u out of range", me);
     *excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) && !c->running[me];  // excludeMySelf
     return sync_device_state(c);
 }
-}  // namespace
 
 int orl_ring_owner_batch_device(orl_ctx* c, uint32_t kind, const uint32_t* d_keys, size_t n, uint32_t me, uint32_t opts,
                                 uint8_t* d_owner, void* stream) {
@@ -2234,7 +1976,7 @@ int orl_ring_owner_batch_device(orl_ctx* c, uint32_t kind, const uint32_t* d_key
     bool excl;
     if (int r = ring_prologue(c, kind, me, opts, &excl)) return r;
     int e = launch_ring_owner(kind, c->d_params, c->d_vr_hash, c->d_vr_silo, c->vr_n_dev, d_keys, n, me, excl, d_owner,
-                              stream ? stream : c->stream);
+                              stream_of(c, stream));
     if (e) return hipfail(c, (hipError_t)e, "ring owner launch");
     return ORL_OK;
 }
@@ -2248,446 +1990,8 @@ int orl_stream_queue_batch_device(orl_ctx* c, uint32_t kind, const uint8_t* d_gu
     bool excl;
     if (int r = ring_prologue(c, kind, me, opts, &excl)) return r;
     int e = launch_stream_queue(kind, c->d_params, c->d_vr_hash, c->d_vr_silo, c->vr_n_dev, d_guids, n, n_queues, me, excl,
-                                d_queue, d_silo, stream ? stream : c->stream);
+                                d_queue, d_silo, stream_of(c, stream));
     if (e) return hipfail(c, (hipError_t)e, "stream queue launch");
-    return ORL_OK;
-}
-
-// ---- f4: directory cache ---------------------------------------------------------------------------
-namespace {
-int cache_config(orl_ctx* c, uint64_t capacity, bool adaptive) {
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (capacity == 0) return fail(c, ORL_E_INVALID, "capacity must be >= 1");
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    ORL_HIP(c, hipDeviceSynchronize());
-    (void)hipFree(c->d_cache); (void)hipFree(c->d_cache2); (void)hipFree(c->d_cclaim); (void)hipFree(c->d_cstate);
-    c->d_cache = nullptr; c->d_cache2 = nullptr; c->d_cclaim = nullptr; c->d_cstate = nullptr;
-    cache_evict_free(&c->cev);
-    cache_sweep_free(&c->csw);
-    c->cache_slots = 0;
-    c->cache_adaptive = false;
-    const uint64_t slots = next_pow2(2 * capacity);
-    // the table, then one u64 LRU generation per slot and the generation base (dir_table_dev.h cache_gens), then, in
-    // adaptive mode, the per-slot adaptive state (orl_internal.h CacheAdaptive)
-    const size_t bytes = cache_table_bytes(slots, adaptive);
-    ORL_HIP(c, hipMalloc((void**)&c->d_cache, bytes));
-    ORL_HIP(c, hipMalloc((void**)&c->d_cache2, bytes));
-    ORL_HIP(c, hipMemset(c->d_cache2, 0, bytes));
-    if (int e = cache_evict_alloc(&c->cev, c->s.max_batch, slots)) return hipfail(c, (hipError_t)e, "cache eviction scratch");
-    if (adaptive)
-        if (int e = cache_sweep_alloc(&c->csw, capacity, slots)) return hipfail(c, (hipError_t)e, "cache sweep scratch");
-    ORL_HIP(c, hipMalloc((void**)&c->d_cclaim, slots * 4));
-    ORL_HIP(c, hipMalloc((void**)&c->d_cstate, 32));
-    ORL_HIP(c, hipMemset(c->d_cache, 0, bytes));
-    ORL_HIP(c, hipMemset(c->d_cclaim, 0xFF, slots * 4));
-    ORL_HIP(c, hipMemset(c->d_cstate, 0, 32));
-    c->cache_slots = slots;
-    c->cache_cap = capacity;
-    c->cache_gen_free = 0;
-    c->cache_ub = c->cache_tombs_ub = 0;
-    c->cache_host_evictions = c->cache_evict_batches = c->cache_rebuilds = c->cache_host_fallbacks = 0;
-    c->cache_adaptive = adaptive;
-    set_cache_on(c, false);
-    return ORL_OK;
-}
-}  // namespace
-
-int orl_cache_config(orl_ctx* c, uint64_t capacity) {
-    if (!c) return ORL_E_INVALID;
-    return cache_config(c, capacity, false);
-}
-
-int orl_cache_config_adaptive(orl_ctx* c, uint64_t capacity, int64_t initial_ttl_ticks, int64_t max_ttl_ticks, double ttl_growth) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    // what keeps the reference's checked arithmetic from throwing: LastRefreshed.Add(ExpirationTimer) and
-    // ExpirationTimer.Multiply(growth) = checked((long)checked((double)ticks * growth)) (StandardExtensions.cs:34-39)
-    if (initial_ttl_ticks < 0 || initial_ttl_ticks > max_ttl_ticks || max_ttl_ticks > ((int64_t)1 << 61))
-        return fail(c, ORL_E_INVALID, "timers must satisfy 0 <= initial <= max <= 2^61 ticks");
-    if (!std::isfinite(ttl_growth) || ttl_growth < 0 || !((double)max_ttl_ticks * ttl_growth < 9223372036854775808.0))
-        return fail(c, ORL_E_INVALID, "growth must be finite, >= 0 and keep max * growth below 2^63");
-    if (int r = cache_config(c, capacity, true)) return r;
-    c->cache_initial_ttl = initial_ttl_ticks;
-    c->cache_max_ttl = max_ttl_ticks;
-    c->cache_growth = ttl_growth;
-    c->cache_now = 0;
-    c->cache_mode = ORL_CACHE_EVICT_DEVICE;  // the host LRU does not carry the adaptive state
-    return ORL_OK;
-}
-
-int orl_cache_clear(orl_ctx* c) {  // LRU.Clear: the entries go, the generation counters run on
-    if (!c) return ORL_E_INVALID;
-    if (!c->cache_slots) return ORL_OK;
-    ORL_HIP(c, hipDeviceSynchronize());
-    ORL_HIP(c, hipMemset(c->d_cache, 0, c->cache_slots * sizeof(DirSlot)));
-    ORL_HIP(c, hipMemset(c->d_cstate, 0, 24));  // the cumulative eviction count runs on
-    c->cache_ub = c->cache_tombs_ub = 0;
-    set_cache_on(c, false);
-    return ORL_OK;
-}
-
-namespace {
-// AddOrUpdate of a batch that can overflow the capacity: the reference's sequential LRU on the host, exactly
-// (AdaptiveGrainDirectoryCache.AddOrUpdate → LRU.Add: AdjustSize — while Count >= MaximumSize free the entry of the next
-// generation, LRU.cs:188-205 — then AddOrUpdate with the next generation, :104-108), over the device table read back, then
-// the table rebuilt and uploaded (no tombstones).  Entries the device path would not keep (an invalid silo, a handle
-// outside this context's space on a local silo: k_cache_probe) are skipped as there.  Generations stay the device's
-// sparse stamps (only their order matters); G advances by n as on the fast path.
-int cache_add_host_lru(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, size_t n) {
-    const uint64_t slots = c->cache_slots, mask = slots - 1;
-    ORL_HIP(c, hipDeviceSynchronize());
-    std::vector<DirSlot> tab(slots);
-    std::vector<uint64_t> gen(slots + 1);
-    ORL_HIP(c, hipMemcpy(tab.data(), c->d_cache, slots * sizeof(DirSlot), hipMemcpyDeviceToHost));
-    ORL_HIP(c, hipMemcpy(gen.data(), reinterpret_cast<uint8_t*>(c->d_cache) + slots * sizeof(DirSlot), (slots + 1) * 8,
-                         hipMemcpyDeviceToHost));
-    std::vector<orl_grain_key> keys(n);
-    std::vector<uint32_t> acts(n);
-    std::vector<uint8_t> silos(n);
-    if (n) {
-        ORL_HIP(c, hipMemcpy(keys.data(), d_keys, n * sizeof(orl_grain_key), hipMemcpyDeviceToHost));
-        ORL_HIP(c, hipMemcpy(acts.data(), d_acts, n * 4, hipMemcpyDeviceToHost));
-        ORL_HIP(c, hipMemcpy(silos.data(), d_silos, n, hipMemcpyDeviceToHost));
-    }
-    struct Ent {
-        orl_grain_key k;
-        uint32_t act;
-        uint8_t silo;
-        uint64_t gen;
-    };
-    auto kk = [](const orl_grain_key& k) { return std::make_tuple(k.type_code_data, k.n0, k.n1); };
-    std::map<std::tuple<uint64_t, uint64_t, uint64_t>, Ent> ents;  // the cache
-    std::map<uint64_t, std::tuple<uint64_t, uint64_t, uint64_t>> by_gen;  // LRU order
-    for (uint64_t i = 0; i < slots; ++i)
-        if (tab[i].state == SLOT_FULL) {
-            const orl_grain_key k{tab[i].tcd, tab[i].n0, tab[i].n1};
-            ents[kk(k)] = Ent{k, tab[i].act, tab[i].silo, gen[i]};
-            by_gen[gen[i]] = kk(k);
-        }
-    const uint64_t G = gen[slots];
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t sl = silos[i];
-        if (!(sl < c->n_silos && (acts[i] < c->cfg.n_act || (acts[i] != ORL_NO_ACT && !c->local[sl])))) continue;
-        while (ents.size() >= c->cache_cap && !by_gen.empty()) {  // AdjustSize
-            auto v = by_gen.begin();
-            c->cache_gen_free = v->first;
-            ++c->cache_host_evictions;
-            ents.erase(v->second);
-            by_gen.erase(v);
-        }
-        const auto key = kk(keys[i]);
-        const uint64_t g = G + i + 1;
-        auto it = ents.find(key);
-        if (it != ents.end()) {
-            by_gen.erase(it->second.gen);
-            it->second = Ent{keys[i], acts[i], (uint8_t)sl, g};
-        } else {
-            ents[key] = Ent{keys[i], acts[i], (uint8_t)sl, g};
-        }
-        by_gen[g] = key;
-    }
-    std::fill(tab.begin(), tab.end(), DirSlot{});
-    std::fill(gen.begin(), gen.end() - 1, 0ull);
-    gen[slots] = G + n;
-    for (const auto& kv : ents) {
-        const Ent& e = kv.second;
-        uint64_t i = dir_slot(jenkins3(e.k.type_code_data, e.k.n0, e.k.n1), mask);
-        while (tab[i].state != SLOT_EMPTY) i = (i + 1) & mask;
-        tab[i].tcd = e.k.type_code_data; tab[i].n0 = e.k.n0; tab[i].n1 = e.k.n1;
-        tab[i].act = e.act; tab[i].silo = e.silo; tab[i].state = SLOT_FULL;
-        gen[i] = e.gen;
-    }
-    ORL_HIP(c, hipMemcpy(c->d_cache, tab.data(), slots * sizeof(DirSlot), hipMemcpyHostToDevice));
-    ORL_HIP(c, hipMemcpy(reinterpret_cast<uint8_t*>(c->d_cache) + slots * sizeof(DirSlot), gen.data(), (slots + 1) * 8,
-                         hipMemcpyHostToDevice));
-    const uint64_t stw[3] = {ents.size(), 0, 0};
-    ORL_HIP(c, hipMemcpy(c->d_cstate, stw, sizeof stw, hipMemcpyHostToDevice));
-    c->cache_ub = ents.size();
-    c->cache_tombs_ub = 0;
-    return ORL_OK;
-}
-}  // namespace
-
-// LRU.Add per entry in batch order, on the caller's stream.  No entry can be evicted while the cache holds <= capacity - n
-// entries before the batch (every add then finds Count < MaximumSize): the plain update (the batch's last writer of a key
-// wins, its generation stamped).  When the host's upper bounds say an eviction is possible, the exact sequential LRU as one
-// preparation, one serial pass and one apply on the device (cache_evict.hip); when they say the table's load (entries +
-// tombstones + new entries) could pass 7/8, a tombstone compaction into the second table first — between the tombstoning
-// and the inserts of an evicting batch, so that even a batch larger than the cache ends with load <= 1/2.  No device-wide
-// sync, no copy to the host.  ORL_CACHE_EVICT_HOST keeps the earlier path (exact counters read back, then the LRU on the
-// host) for A/B runs and as the tests' cross-check.
-// On an adaptive cache every entry the batch leaves is a new GrainDirectoryCacheEntry (AdaptiveGrainDirectoryCache.cs:
-// 97-103): d_etags[i] (0 when null), the initial timer, LastRefreshed = the context's `cache_now`, NumAccesses = 0.
-namespace {
-int cache_add(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos, const int32_t* d_etags,
-              size_t n, void* stream) {
-    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
-    CacheFresh fresh;
-    if (c->cache_adaptive) {
-        fresh.etags = d_etags;
-        fresh.now = c->cache_now;
-        fresh.initial_ttl = c->cache_initial_ttl;
-        fresh.on = 1;
-    }
-    if (n && (!d_keys || !d_acts || !d_silos)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    auto fits = [&](uint64_t cnt, uint64_t tombs) {  // no eviction possible, and the table's load stays <= 7/8
-        return cnt + n <= c->cache_cap && (cnt + tombs + n) * 8 <= c->cache_slots * 7;
-    };
-    int r = sync_device_state(c);
-    if (r) return r;
-    set_cache_on(c, true);
-    if ((r = sync_device_state(c))) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const uint64_t mask = c->cache_slots - 1;
-    if (!fits(c->cache_ub, c->cache_tombs_ub)) {
-        if (c->cache_mode == ORL_CACHE_EVICT_HOST) {  // exact counters (a sync), then the host LRU if still needed
-            ORL_HIP(c, hipDeviceSynchronize());
-            uint64_t stw[3];
-            ORL_HIP(c, hipMemcpy(stw, c->d_cstate, sizeof stw, hipMemcpyDeviceToHost));
-            c->cache_ub = stw[0];
-            c->cache_tombs_ub = stw[1];
-            if (!fits(c->cache_ub, c->cache_tombs_ub)) {
-                ++c->cache_host_fallbacks;
-                return cache_add_host_lru(c, d_keys, d_acts, d_silos, n);
-            }
-        } else {
-            if (n == 0) return ORL_OK;
-            const uint64_t fresh_ub = std::min<uint64_t>(n, c->cache_cap);  // the batch leaves at most capacity entries
-            const bool evicts = c->cache_ub + n > c->cache_cap;
-            const bool crowded = (c->cache_ub + c->cache_tombs_ub + (evicts ? fresh_ub : n)) * 8 > c->cache_slots * 7;
-            if (evicts) {
-                int e = launch_cache_evict_add(c->d_cache, mask, crowded ? c->d_cache2 : nullptr, c->d_cstate, c->cache_cap, d_keys,
-                                               d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st, fresh);
-                if (e) return hipfail(c, (hipError_t)e, "cache eviction launch");
-                ++c->cache_evict_batches;
-                // FULL + TOMB slots grow by at most the new entries (an eviction turns a FULL slot into a tombstone)
-                const uint64_t occupied = c->cache_ub + c->cache_tombs_ub + fresh_ub;
-                c->cache_ub = std::min(c->cache_ub + n, c->cache_cap);
-                c->cache_tombs_ub = occupied > c->cache_ub ? occupied - c->cache_ub : 0;
-                if (crowded) {  // compacted after the tombstoning: what is left is the batch's result, no tombstones
-                    std::swap(c->d_cache, c->d_cache2);
-                    ++c->cache_rebuilds;
-                    c->cache_tombs_ub = 0;
-                }
-                return ORL_OK;
-            }
-            // no eviction possible, only tombstones in the way: compact, then the plain update below
-            int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st, c->cache_adaptive);
-            if (e) return hipfail(c, (hipError_t)e, "cache rebuild launch");
-            std::swap(c->d_cache, c->d_cache2);
-            ++c->cache_rebuilds;
-            c->cache_tombs_ub = 0;
-        }
-    }
-    int e = launch_cache_update(c->d_cache, mask, c->d_cclaim, c->d_cstate, d_keys, d_acts, d_silos, n, c->cfg.n_act,
-                                c->n_silos, c->d_dslot, c->d_dflag, reinterpret_cast<uint32_t*>(c->d_cstate + 2), st, c->d_params,
-                                fresh);
-    if (e) return hipfail(c, (hipError_t)e, "cache update launch");
-    c->cache_ub += n;
-    return ORL_OK;
-}
-
-// The adaptive calls' common refusals.
-int need_adaptive(orl_ctx* c) {
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!c->cache_slots || !c->cache_adaptive)
-        return fail(c, ORL_E_STATE, "directory cache not configured in adaptive mode (orl_cache_config_adaptive)");
-    return ORL_OK;
-}
-}  // namespace
-
-int orl_cache_add_or_update_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                                   size_t n, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    return cache_add(c, d_keys, d_acts, d_silos, nullptr, n, stream);
-}
-
-int orl_cache_add_or_update_versioned_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts,
-                                             const uint8_t* d_silos, const int32_t* d_etags, size_t n, int64_t now_ticks,
-                                             void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (int r = need_adaptive(c)) return r;
-    if (n && !d_etags) return fail(c, ORL_E_INVALID, "null device buffer");
-    c->cache_now = now_ticks;
-    return cache_add(c, d_keys, d_acts, d_silos, d_etags, n, stream);
-}
-
-// One pass of the maintainer (cache_adaptive.hip).  The host's bounds stay as they are: the pass turns FULL slots into
-// tombstones and nothing else, so the entries only shrink (cache_ub bounds them still) and the occupied slots, FULL +
-// TOMB, do not change (cache_ub + cache_tombs_ub bounds them still) — and the add's path choice reads the bounds only
-// as cache_ub alone and as that sum.
-int orl_cache_maintain_device(orl_ctx* c, uint32_t me, uint32_t opts, int64_t now_ticks, struct orl_cache_sweep* out,
-                              void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (int r = need_adaptive(c)) return r;
-    if (!out) return fail(c, ORL_E_INVALID, "null result struct");
-    if (me >= c->n_silos) return fail(c, ORL_E_INVALID, "silo %u out of range", me);
-    if (int r = sync_device_state(c)) return r;
-    c->cache_now = now_ticks;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_cache_sweep(c->d_params, c->d_cache, c->cache_slots - 1, c->d_cstate, me,
-                               (opts & ORL_OPT_EXCLUDE_IF_STOPPING) != 0, c->n_silos, now_ticks, c->csw, st);
-    if (e) return hipfail(c, (hipError_t)e, "cache sweep launch");
-    out->d_keys = c->csw.keys;
-    out->d_etags = c->csw.etags;
-    out->d_owner_offsets = c->csw.owner_off;
-    out->d_counts = c->csw.counts;
-    return ORL_OK;
-}
-
-int orl_cache_mark_fresh_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, int64_t now_ticks, uint8_t* d_found,
-                                void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (int r = need_adaptive(c)) return r;
-    if (n && !d_keys) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    c->cache_now = now_ticks;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_cache_mark_fresh(c->d_cache, c->cache_slots - 1, d_keys, n, now_ticks, c->cache_max_ttl, c->cache_growth, d_found,
-                                    st);
-    if (e) return hipfail(c, (hipError_t)e, "cache mark-fresh launch");
-    return ORL_OK;
-}
-
-// ProcessCacheRefreshResponse (AdaptiveDirectoryCacheMaintainer.cs:167-207) over the owner's whole answer, on the
-// caller's stream (cache_evict.hip).  The path choice is the versioned add's, from the host's upper bounds
-// with n as the bound on new entries: no eviction possible → the data-parallel apply alone (after a compaction when the
-// load bound asks for one); else the selection and the serial pass are enqueued too — they leave at once on the device
-// when the response holds no valid ADD, which the host cannot know — with the compaction between the tombstoning and the
-// inserts when the load bound asks for it.  Removes only turn FULL slots into tombstones: the bounds hold as after a sweep.
-int orl_cache_apply_refresh_device(orl_ctx* c, const orl_grain_key* d_keys, const uint8_t* d_kind, const int32_t* d_etags,
-                                   const uint32_t* d_acts, const uint8_t* d_silos, size_t n, int64_t now_ticks,
-                                   uint8_t* d_present, uint64_t* d_counts, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (int r = need_adaptive(c)) return r;
-    if (n && (!d_keys || !d_kind || !d_etags || !d_acts || !d_silos)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    c->cache_now = now_ticks;
-    int r = sync_device_state(c);
-    if (r) return r;
-    set_cache_on(c, true);
-    if ((r = sync_device_state(c))) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const uint64_t mask = c->cache_slots - 1;
-    CacheFresh fresh;
-    fresh.etags = d_etags;
-    fresh.now = now_ticks;
-    fresh.initial_ttl = c->cache_initial_ttl;
-    fresh.on = 1;
-    CacheRefresh rf;
-    rf.kind = d_kind;
-    rf.max_ttl = c->cache_max_ttl;
-    rf.growth = c->cache_growth;
-    rf.present = d_present;
-    rf.counts = d_counts;
-    const bool evicts = c->cache_ub + n > c->cache_cap;
-    const uint64_t fresh_ub = evicts ? std::min<uint64_t>(n, c->cache_cap) : n;  // an evicting call leaves at most capacity entries
-    const bool crowded = (c->cache_ub + c->cache_tombs_ub + fresh_ub) * 8 > c->cache_slots * 7;
-    if (crowded && !evicts && n) {  // only tombstones in the way: compact first
-        int e = launch_cache_rebuild(c->d_cache, c->d_cache2, mask, c->d_cstate, c->cev, st, true);
-        if (e) return hipfail(c, (hipError_t)e, "cache rebuild launch");
-        std::swap(c->d_cache, c->d_cache2);
-        ++c->cache_rebuilds;
-        c->cache_tombs_ub = 0;
-    }
-    int e = launch_cache_apply_refresh(c->d_cache, mask, crowded && evicts ? c->d_cache2 : nullptr, c->d_cstate, c->cache_cap, d_keys,
-                                       d_acts, d_silos, n, c->cfg.n_act, c->n_silos, c->d_params->local, c->cev, st, fresh, rf,
-                                       evicts);
-    if (e) return hipfail(c, (hipError_t)e, "cache refresh-apply launch");
-    if (n == 0) return ORL_OK;
-    const uint64_t occupied = c->cache_ub + c->cache_tombs_ub + fresh_ub;  // FULL + TOMB slots grow by at most the new entries
-    c->cache_ub = std::min(c->cache_ub + n, c->cache_cap);
-    c->cache_tombs_ub = occupied > c->cache_ub ? occupied - c->cache_ub : 0;
-    if (evicts) {
-        ++c->cache_evict_batches;
-        if (crowded) {
-            std::swap(c->d_cache, c->d_cache2);
-            ++c->cache_rebuilds;
-            c->cache_tombs_ub = 0;
-        }
-    }
-    return ORL_OK;
-}
-
-int orl_cache_adjust_for_removed_silo_device(orl_ctx* c, uint32_t me, uint32_t opts, uint32_t removed_silo,
-                                             uint64_t* d_removed_count, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
-    if (me >= c->n_silos || removed_silo >= c->n_silos) return fail(c, ORL_E_INVALID, "silo out of range");
-    if (int r = sync_device_state(c)) return r;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_cache_adjust(c->d_params, c->d_cache, c->cache_slots - 1, c->d_cstate, me,
-                                (opts & ORL_OPT_EXCLUDE_IF_STOPPING) != 0, c->n_silos, removed_silo, d_removed_count, st);
-    if (e) return hipfail(c, (hipError_t)e, "cache adjust launch");
-    return ORL_OK;  // the host's bounds stay valid, as after a sweep
-}
-
-int orl_cache_peek_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, uint32_t* d_act, uint8_t* d_silo, int32_t* d_etag,
-                          int64_t* d_ttl, int64_t* d_last_refreshed, uint8_t* d_accessed, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
-    if (!c->cache_adaptive && (d_etag || d_ttl || d_last_refreshed || d_accessed))
-        return fail(c, ORL_E_STATE, "etag, timer, refresh time and access mark exist only in an adaptive cache");
-    if (n && !d_keys) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_cache_peek(c->d_cache, c->cache_slots - 1, c->cache_adaptive, d_keys, n, d_act, d_silo, d_etag, d_ttl,
-                              d_last_refreshed, d_accessed, st);
-    if (e) return hipfail(c, (hipError_t)e, "cache peek launch");
-    return ORL_OK;
-}
-
-int orl_cache_remove_device(orl_ctx* c, const orl_grain_key* d_keys, size_t n, uint8_t* d_removed, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
-    if (n && (!d_keys || !d_removed)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_dir_remove(c->d_cache, c->cache_slots - 1, c->d_cclaim, c->d_cstate, d_keys, n, c->d_dslot, d_removed, st);
-    if (e) return hipfail(c, (hipError_t)e, "cache remove launch");
-    c->cache_tombs_ub += n;
-    return ORL_OK;
-}
-
-int orl_cache_stats(orl_ctx* c, struct orl_cache_stats* out) {
-    if (!c || !out) return ORL_E_INVALID;
-    *out = {};
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!c->cache_slots) return fail(c, ORL_E_STATE, "directory cache not configured (orl_cache_config)");
-    ORL_HIP(c, hipDeviceSynchronize());
-    uint64_t st[4];
-    ORL_HIP(c, hipMemcpy(st, c->d_cstate, sizeof st, hipMemcpyDeviceToHost));
-    out->entries = st[0];
-    out->tombstones = st[1];
-    out->evictions = st[3] + c->cache_host_evictions;
-    out->evict_batches = c->cache_evict_batches;
-    out->rebuilds = c->cache_rebuilds;
-    out->host_fallbacks = c->cache_host_fallbacks;
-    if ((uint32_t)st[2]) return fail(c, ORL_E_STATE, "directory cache: the device raised error word 0x%x", (unsigned)(uint32_t)st[2]);
-    return ORL_OK;
-}
-
-int orl_cache_evict_mode(orl_ctx* c, uint32_t mode) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (mode != ORL_CACHE_EVICT_DEVICE && mode != ORL_CACHE_EVICT_HOST) return fail(c, ORL_E_INVALID, "unknown eviction mode %u", mode);
-    if (mode == ORL_CACHE_EVICT_HOST && c->cache_adaptive)
-        return fail(c, ORL_E_STATE, "the host LRU does not carry an adaptive cache's per-entry state");
-    c->cache_mode = mode;
-    return ORL_OK;
-}
-
-int orl_cache_count(orl_ctx* c, uint64_t* n) {
-    if (!c || !n) return ORL_E_INVALID;
-    *n = 0;
-    if (!c->cache_slots) return ORL_OK;
-    ORL_HIP(c, hipDeviceSynchronize());
-    uint64_t st[3];
-    ORL_HIP(c, hipMemcpy(st, c->d_cstate, sizeof st, hipMemcpyDeviceToHost));
-    *n = st[0];
     return ORL_OK;
 }
 
@@ -2700,7 +2004,7 @@ int orl_outbound_queues_device(orl_ctx* c, const orl_msg_hdr* d_msgs, const uint
     if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
     if (int r = sync_device_state(c)) return r;
     int e = launch_outbound_queues(d_msgs, d_route, n, n_senders, c->d_silo_hash, c->d_silo_known, d_queue,
-                                   stream ? stream : c->stream);
+                                   stream_of(c, stream));
     if (e) return hipfail(c, (hipError_t)e, "outbound queues launch");
     return ORL_OK;
 }
@@ -2712,335 +2016,9 @@ int orl_client_buckets_device(orl_ctx* c, const orl_msg_hdr* d_msgs, size_t n, u
     // above 2^30, ((key % mod) + mod) can pass int.MaxValue: the reference's checked((uint)key) then throws
     if (n_buckets == 0 || n_buckets > (1u << 30)) return fail(c, ORL_E_INVALID, "n_buckets must be in [1, 2^30]");
     if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    int e = launch_client_buckets(d_msgs, n, n_buckets, d_bucket, stream ? stream : c->stream);
+    if (int r = need_device(c)) return r;
+    int e = launch_client_buckets(d_msgs, n, n_buckets, d_bucket, stream_of(c, stream));
     if (e) return hipfail(c, (hipError_t)e, "client buckets launch");
-    return ORL_OK;
-}
-
-}  // extern "C"
-
-// ---- stateless-worker grains: the local catalog's host mirror -----------------------------------------
-namespace {
-
-// The mirror after orl_sw_set_busy_device: wait for that stream, then read the table back (only busy bits can differ).
-int sw_sync_host(orl_ctx* c) {
-    if (!c->sw_dev_newer) return ORL_OK;
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    ORL_HIP(c, hipStreamSynchronize(c->sw_dev_stream));
-    if (c->d_sw && c->d_sw_slots == c->sw_table.size())
-        ORL_HIP(c, hipMemcpy(c->sw_table.data(), c->d_sw, c->sw_table.size() * sizeof(SwSlot), hipMemcpyDeviceToHost));
-    c->sw_dev_newer = false;
-    return ORL_OK;
-}
-
-void sw_clear(orl_ctx* c, uint64_t slots) {
-    c->sw_table.assign(slots, SwSlot{});
-    c->sw_mask = slots ? slots - 1 : 0;
-    c->sw_count = c->sw_tombs = 0;
-    c->sw_dirty = true;
-    c->sw_dev_newer = false;
-}
-
-int sw_type_index(const orl_ctx* c, uint64_t tcd) {
-    for (uint32_t i = 0; i < c->sw_n; ++i)
-        if (c->sw_tcd[i] == tcd) return (int)i;
-    return -1;
-}
-
-// Slot of (key, silo) in the mirror, or -1; *free_slot = the first reusable slot (tombstone or chain end) of the chain.
-int64_t sw_find(const orl_ctx* c, const orl_grain_key& k, uint32_t silo, int64_t* free_slot) {
-    int64_t fr = -1;
-    if (!c->sw_table.empty()) {
-        uint64_t i = sw_start(jenkins3(k.type_code_data, k.n0, k.n1), silo, c->sw_mask);
-        for (uint64_t step = 0; step <= c->sw_mask; ++step) {
-            const SwSlot& s = c->sw_table[i];
-            if (s.state == SLOT_EMPTY) { if (fr < 0) fr = (int64_t)i; break; }
-            if (s.state == SLOT_TOMB) { if (fr < 0) fr = (int64_t)i; }
-            else if (s.silo == silo && s.tcd == k.type_code_data && s.n0 == k.n0 && s.n1 == k.n1) {
-                if (free_slot) *free_slot = fr;
-                return (int64_t)i;
-            }
-            i = (i + 1) & c->sw_mask;
-        }
-    }
-    if (free_slot) *free_slot = fr;
-    return -1;
-}
-
-int sw_pos(const SwSlot& s, uint32_t act) {
-    for (uint32_t p = 0; p < s.count; ++p)
-        if (s.act[p] == act) return (int)p;
-    return -1;
-}
-
-// Rebuild the mirror without tombstones (same slot count).
-void sw_rehash(orl_ctx* c) {
-    std::vector<SwSlot> old;
-    old.swap(c->sw_table);
-    c->sw_table.assign(old.size(), SwSlot{});
-    c->sw_tombs = 0;
-    for (const SwSlot& s : old) {
-        if (s.state != SLOT_FULL) continue;
-        uint64_t i = sw_start(jenkins3(s.tcd, s.n0, s.n1), s.silo, c->sw_mask);
-        while (c->sw_table[i].state != SLOT_EMPTY) i = (i + 1) & c->sw_mask;
-        c->sw_table[i] = s;
-    }
-    c->sw_dirty = true;
-}
-
-bool sw_item_ok(const orl_ctx* c, const orl_grain_key& k, uint32_t act, uint32_t silo) {
-    return sw_type_index(c, k.type_code_data) >= 0 && act < c->cfg.n_act && silo < c->n_silos;
-}
-
-}  // namespace
-
-extern "C" {
-
-int orl_sw_types_set(orl_ctx* c, const uint64_t* tcd, const uint8_t* max_local, uint32_t n) {
-    if (!c) return ORL_E_INVALID;
-    if (n > ORL_MAX_SW_TYPES) return fail(c, ORL_E_INVALID, "stateless-worker types: n = %u (at most %u)", n, ORL_MAX_SW_TYPES);
-    if (n && (!tcd || !max_local)) return fail(c, ORL_E_INVALID, "null type or MaxLocal array");
-    for (uint32_t i = 0; i < n; ++i) {
-        if ((uint32_t)(tcd[i] >> 56) != ORL_CAT_GRAIN)  // GrainTypeData describes grain classes (GrainTypeData.cs:43-50)
-            return fail(c, ORL_E_INVALID, "stateless-worker type %u: category %u is not ORL_CAT_GRAIN", i, (uint32_t)(tcd[i] >> 56));
-        if (max_local[i] < 1 || max_local[i] > ORL_SW_MAX_LOCAL)
-            return fail(c, ORL_E_INVALID, "stateless-worker type %u: MaxLocal %u outside 1..%u", i, max_local[i], ORL_SW_MAX_LOCAL);
-        for (uint32_t j = 0; j < i; ++j)
-            if (tcd[i] == tcd[j]) return fail(c, ORL_E_INVALID, "stateless-worker types: entry %u repeats entry %u", i, j);
-    }
-    c->sw_n = n;
-    std::memset(c->sw_tcd, 0, sizeof c->sw_tcd);
-    std::memset(c->sw_max, 0, sizeof c->sw_max);
-    for (uint32_t i = 0; i < n; ++i) {
-        c->sw_tcd[i] = tcd[i];
-        c->sw_max[i] = max_local[i];
-    }
-    // the lists were kept under the old types' MaxLocal: start over (a first set sizes the catalog for 1024 entries)
-    sw_clear(c, n && c->sw_table.empty() ? next_pow2(2 * 1024) : c->sw_table.size());
-    return ORL_OK;
-}
-
-int orl_sw_config(orl_ctx* c, uint64_t capacity) {
-    if (!c) return ORL_E_INVALID;
-    if (capacity > (1ull << 30)) return fail(c, ORL_E_INVALID, "catalog capacity %llu too large", (unsigned long long)capacity);
-    sw_clear(c, next_pow2(2 * std::max<uint64_t>(capacity, 1)));
-    return ORL_OK;
-}
-
-int orl_sw_add(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n, uint8_t* status) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!keys || !acts || !silos || !status)) return fail(c, ORL_E_INVALID, "null array");
-    if (int r = sw_sync_host(c)) return r;
-    // entries this batch can create: the distinct (grain, silo) pairs of supported items that have no entry yet
-    std::vector<std::pair<orl_grain_key, uint32_t>> fresh;
-    for (size_t i = 0; i < n; ++i) {
-        if (!sw_item_ok(c, keys[i], acts[i], silos[i]) || sw_find(c, keys[i], silos[i], nullptr) >= 0) continue;
-        bool seen = false;
-        for (const auto& f : fresh)
-            seen = seen || (f.second == silos[i] && f.first.type_code_data == keys[i].type_code_data && f.first.n0 == keys[i].n0 &&
-                            f.first.n1 == keys[i].n1);
-        if (!seen) fresh.push_back({keys[i], silos[i]});
-        if (fresh.size() > c->sw_table.size()) break;  // already past any capacity
-    }
-    if ((c->sw_count + fresh.size()) * 2 > c->sw_table.size())
-        return fail(c, ORL_E_CAPACITY, "stateless-worker catalog full: %llu + %zu entries, %zu slots (orl_sw_config)",
-                    (unsigned long long)c->sw_count, fresh.size(), c->sw_table.size());
-    if ((c->sw_count + c->sw_tombs + fresh.size()) * 2 > c->sw_table.size()) sw_rehash(c);
-    for (size_t i = 0; i < n; ++i) {
-        const int t = sw_type_index(c, keys[i].type_code_data);
-        if (!sw_item_ok(c, keys[i], acts[i], silos[i])) { status[i] = ORL_SW_UNSUPPORTED; continue; }
-        int64_t fr = -1;
-        const int64_t at = sw_find(c, keys[i], silos[i], &fr);
-        if (at >= 0) {
-            SwSlot& s = c->sw_table[at];
-            if (sw_pos(s, acts[i]) >= 0) { status[i] = ORL_SW_UNSUPPORTED; continue; }
-            if (s.count >= s.max_local) { status[i] = ORL_SW_DUPLICATE; continue; }  // Catalog.cs:1176-1180
-            s.act[s.count++] = acts[i];  // appended, idle (its busy bit is clear: removal keeps the bits above count zero)
-        } else {
-            SwSlot& s = c->sw_table[fr];
-            if (s.state == SLOT_TOMB) --c->sw_tombs;
-            s = SwSlot{};
-            s.tcd = keys[i].type_code_data; s.n0 = keys[i].n0; s.n1 = keys[i].n1;
-            s.silo = silos[i];
-            s.count = 1;
-            s.state = SLOT_FULL;
-            s.max_local = c->sw_max[t];
-            s.act[0] = acts[i];
-            ++c->sw_count;
-        }
-        status[i] = ORL_SW_ADDED;
-        c->sw_dirty = true;
-    }
-    return ORL_OK;
-}
-
-int orl_sw_remove(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, size_t n, uint8_t* removed) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!keys || !acts || !silos)) return fail(c, ORL_E_INVALID, "null array");
-    if (int r = sw_sync_host(c)) return r;
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
-        const int p = at >= 0 ? sw_pos(c->sw_table[at], acts[i]) : -1;
-        if (removed) removed[i] = p >= 0 ? 1 : 0;
-        if (p < 0) continue;
-        SwSlot& s = c->sw_table[at];
-        for (uint32_t q = (uint32_t)p; q + 1 < s.count; ++q) s.act[q] = s.act[q + 1];  // List.Remove: the order stays
-        s.act[--s.count] = 0;
-        s.busy = (uint8_t)((s.busy & ((1u << p) - 1u)) | ((s.busy >> (p + 1)) << p));
-        if (s.count == 0) {  // an emptied list frees its entry
-            s = SwSlot{};
-            s.state = SLOT_TOMB;
-            --c->sw_count;
-            ++c->sw_tombs;
-        }
-        c->sw_dirty = true;
-    }
-    return ORL_OK;
-}
-
-int orl_sw_set_busy(orl_ctx* c, const orl_grain_key* keys, const uint32_t* acts, const uint8_t* silos, const uint8_t* busy,
-                    size_t n, uint8_t* found) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!keys || !acts || !silos || !busy)) return fail(c, ORL_E_INVALID, "null array");
-    if (int r = sw_sync_host(c)) return r;
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
-        const int p = at >= 0 ? sw_pos(c->sw_table[at], acts[i]) : -1;
-        if (found) found[i] = p >= 0 ? 1 : 0;
-        if (p < 0) continue;
-        SwSlot& s = c->sw_table[at];
-        const uint8_t b = busy[i] ? (uint8_t)(s.busy | (1u << p)) : (uint8_t)(s.busy & ~(1u << p));
-        if (b != s.busy) {
-            s.busy = b;
-            c->sw_dirty = true;
-        }
-    }
-    return ORL_OK;
-}
-
-int orl_sw_set_busy_device(orl_ctx* c, const orl_grain_key* d_keys, const uint32_t* d_acts, const uint8_t* d_silos,
-                           const uint8_t* d_busy, size_t n, uint8_t* d_found, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!d_keys || !d_acts || !d_silos || !d_busy)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
-    if (c->sw_n == 0) return fail(c, ORL_E_STATE, "no stateless-worker types set (orl_sw_types_set)");
-    if (int r = sync_device_state(c)) return r;  // host changes first (refuses a host-only context)
-    if (!c->d_sw) return fail(c, ORL_E_STATE, "no stateless-worker catalog on the device");
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int e = launch_sw_set_busy(c->d_sw, c->sw_mask, d_keys, d_acts, d_silos, d_busy, n, d_found, st);
-    if (e) return hipfail(c, (hipError_t)e, "busy-bit launch");
-    if (n) {
-        c->sw_dev_newer = true;
-        c->sw_dev_stream = st;
-    }
-    return ORL_OK;
-}
-
-int orl_sw_lookup_host(orl_ctx* c, const orl_grain_key* keys, const uint8_t* silos, size_t n, uint8_t* count, uint32_t* acts,
-                       uint8_t* busy_mask) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!keys || !silos || !count || !acts || !busy_mask)) return fail(c, ORL_E_INVALID, "null array");
-    if (int r = sw_sync_host(c)) return r;
-    for (size_t i = 0; i < n; ++i) {
-        const int64_t at = sw_find(c, keys[i], silos[i], nullptr);
-        count[i] = at >= 0 ? c->sw_table[at].count : 0;
-        busy_mask[i] = at >= 0 ? c->sw_table[at].busy : 0;
-        for (uint32_t p = 0; p < ORL_SW_MAX_LOCAL; ++p)
-            acts[i * ORL_SW_MAX_LOCAL + p] = (at >= 0 && p < c->sw_table[at].count) ? c->sw_table[at].act[p] : ORL_NO_ACT;
-    }
-    return ORL_OK;
-}
-
-int orl_sw_count(orl_ctx* c, uint64_t* n) {
-    if (!c || !n) return ORL_E_INVALID;
-    *n = c->sw_count;
-    return ORL_OK;
-}
-
-// ---- f2: wire codec ---------------------------------------------------------------------------------
-int orl_silo_address_set(orl_ctx* c, uint32_t silo, const uint8_t* ip16, int32_t port, int32_t generation) {
-    if (!c) return ORL_E_INVALID;
-    if (silo >= 255) return fail(c, ORL_E_INVALID, "silo index %u out of range (< 255)", silo);
-    if (!ip16) {
-        c->silo_addr_known[silo] = 0;
-        c->silo_addr_dirty = true;
-        return ORL_OK;
-    }
-    if (port < 0 || port > 65535) return fail(c, ORL_E_INVALID, "port %d out of range", port);
-    uint32_t w[6];
-    std::memcpy(w, ip16, 16);
-    w[4] = (uint32_t)port;
-    w[5] = (uint32_t)generation;
-    for (uint32_t s = 0; s < 255; ++s)
-        if (s != silo && c->silo_addr_known[s] && std::memcmp(c->silo_addr[s], w, sizeof w) == 0)
-            return fail(c, ORL_E_INVALID, "address already belongs to silo %u", s);
-    std::memcpy(c->silo_addr[silo], w, sizeof w);
-    c->silo_addr_known[silo] = 1;
-    c->silo_addr_dirty = true;
-    return ORL_OK;
-}
-
-int orl_decode_frames_device(orl_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_frame_offsets, size_t n,
-                             uint32_t sender_override, orl_msg_hdr* d_out, uint8_t* d_status, uint32_t* d_n_bad, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (n && (!d_bytes || !d_frame_offsets || !d_out || !d_status)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if ((uintptr_t)d_bytes & 3u) return fail(c, ORL_E_INVALID, "frame buffer must be 4-byte aligned");
-    if (sender_override > ORL_SENDER_FROM_HEADER) return fail(c, ORL_E_INVALID, "sender_override must be < 255 or 0xFF");
-    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
-    if (int r = sync_device_state(c)) return r;
-    int e = launch_decode_frames(d_bytes, nbytes, d_frame_offsets, n, sender_override, c->d_silo_tab, d_out, d_status,
-                                 d_n_bad, c->d_decode_flag, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "decode frames launch");
-    return ORL_OK;
-}
-
-int orl_grain_type_set(orl_ctx* c, int32_t type_code, const char* utf8, size_t len) {
-    if (!c) return ORL_E_INVALID;
-    if (len == 0 || !utf8) {
-        c->grain_types.erase(type_code);
-        c->gt_dirty = true;
-        return ORL_OK;
-    }
-    size_t total = len;
-    for (const auto& kv : c->grain_types)
-        if (kv.first != type_code) total += kv.second.size();
-    if (total > kGrainTypeBlob) return fail(c, ORL_E_CAPACITY, "grain type names exceed %u bytes", kGrainTypeBlob);
-    if (c->grain_types.size() >= kGrainTypeSlots / 2 && !c->grain_types.count(type_code))
-        return fail(c, ORL_E_CAPACITY, "more than %u grain types", kGrainTypeSlots / 2);
-    c->grain_types[type_code] = std::string(utf8, len);
-    c->gt_dirty = true;
-    return ORL_OK;
-}
-
-int orl_stamp_frames_device(orl_ctx* c, const uint8_t* d_bytes, uint64_t nbytes, const uint64_t* d_frame_offsets, size_t n,
-                            const uint32_t* d_route, const uint32_t* d_act, const orl_grain_key* d_act_keys, uint32_t n_act_keys,
-                            const orl_grain_key* d_new_act_keys, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offsets,
-                            uint64_t* d_out_total, uint8_t* d_status, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!d_out_total) return fail(c, ORL_E_INVALID, "null total pointer");
-    if (n && (!d_bytes || !d_frame_offsets || !d_route || !d_act || !d_out || !d_out_offsets || !d_status))
-        return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n_act_keys && !d_act_keys) return fail(c, ORL_E_INVALID, "null activation key table");
-    if (((uintptr_t)d_bytes & 3u) || ((uintptr_t)d_out & 3u)) return fail(c, ORL_E_INVALID, "frame buffers must be 4-byte aligned");
-    if (n > 0xFFFFFFFFull) return fail(c, ORL_E_CAPACITY, "batch too large");
-    if (int r = sync_device_state(c)) return r;
-    if (n > c->stamp_cap) {  // scratch grows to the largest batch seen (a synchronising allocation, once)
-        if (c->d_stamp_sizes) (void)hipFree(c->d_stamp_sizes);
-        if (c->d_stamp_temp) (void)hipFree(c->d_stamp_temp);
-        c->d_stamp_sizes = nullptr;
-        c->d_stamp_temp = nullptr;
-        c->stamp_cap = 0;
-        const size_t tb = stamp_scan_temp_bytes(n);
-        ORL_HIP(c, hipMalloc((void**)&c->d_stamp_sizes, (n + 1) * sizeof(uint64_t)));  // + the deferral flag
-        ORL_HIP(c, hipMalloc(&c->d_stamp_temp, std::max<size_t>(tb, 16)));
-        c->stamp_cap = n;
-        c->stamp_temp_bytes = std::max<size_t>(tb, 16);
-    }
-    int e = launch_stamp_frames(d_bytes, nbytes, d_frame_offsets, n, d_route, d_act, d_act_keys, n_act_keys, d_new_act_keys,
-                                c->d_gt, c->d_gt_blob, c->d_silo_words, c->d_stamp_sizes, c->d_stamp_temp, c->stamp_temp_bytes,
-                                d_out, out_cap, d_out_offsets, d_out_total, d_status, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "stamp frames launch");
     return ORL_OK;
 }
 
@@ -3053,192 +2031,11 @@ int orl_sync(orl_ctx* c) {
 
 int orl_bucket_device(orl_ctx* c, const uint32_t* d_act, size_t n, uint32_t* d_order, uint32_t* d_off, void* stream) {
     if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (!d_off || (n && (!d_act || !d_order))) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    int e = launch_bucket_acts(d_act, n, c->cfg.n_act, d_order, d_off, c->s, stream ? stream : c->stream);
+    if (int r = check_batch(c, n)) return r;
+    int e = launch_bucket_acts(d_act, n, c->cfg.n_act, d_order, d_off, c->s, stream_of(c, stream));
     if (e) return hipfail(c, (hipError_t)e, "bucket launch");
-    return ORL_OK;
-}
-
-int orl_admit_device(orl_ctx* c, const uint32_t* d_act, const uint8_t* d_mflags, size_t n, const uint32_t* d_order,
-                     const uint32_t* d_off, orl_act_state* d_state, const orl_admit_limits* limits, uint8_t* d_disp,
-                     uint64_t* d_counts, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!limits) return fail(c, ORL_E_INVALID, "null limits");
-    if (n && (!d_act || !d_mflags || !d_order || !d_off || !d_state || !d_disp)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    if (!c->adm.base) {  // a synchronising allocation, once
-        ORL_HIP(c, hipSetDevice(c->cfg.device));
-        if (int e = admit_alloc(&c->adm, c->s.max_batch)) return hipfail(c, (hipError_t)e, "admission scratch");
-    }
-    int e = launch_admit(d_mflags, n, c->cfg.n_act, d_order, d_off, d_state, *limits, d_disp, d_counts, c->adm,
-                         stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "admission launch");
-    return ORL_OK;
-}
-
-// ---- waiting queues (waitq.hip) ---------------------------------------------------------------------------
-int orl_waitq_create(orl_ctx* c, uint64_t capacity, orl_waitq** out) {
-    if (!c || !out) return ORL_E_INVALID;
-    *out = nullptr;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (capacity == 0 || capacity >= 0xFFFFFFFFull) return fail(c, ORL_E_INVALID, "waiting queue capacity must be in 1 .. 2^32 - 2");
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    if (int e = waitq_alloc(out, c->cfg.n_act, capacity, c->s.max_batch))
-        return fail(c, ORL_E_NOMEM, "waiting queue of %llu records: %s", (unsigned long long)capacity,
-                    hipGetErrorString((hipError_t)e));
-    return ORL_OK;
-}
-
-int orl_waitq_destroy(orl_ctx* c, orl_waitq* q) {
-    if (!c) return ORL_E_INVALID;
-    if (!q) return ORL_OK;
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    waitq_free(q);
-    return ORL_OK;
-}
-
-int orl_waitq_view_get(orl_ctx* c, orl_waitq* q, orl_waitq_view* out) {
-    if (!c || !q || !out) return ORL_E_INVALID;
-    const uint32_t b = q->cur;
-    *out = orl_waitq_view{q->off[b], q->tok[b], q->act[b], q->mflags[b], q->running_tok, q->out_tok,
-                          q->out_act, q->out_mflags, q->out_kind, q->out_n, q->waiting_n};
-    return ORL_OK;
-}
-
-int orl_waitq_append_device(orl_ctx* c, orl_waitq* q, const uint32_t* d_tok, const uint8_t* d_mflags, size_t n,
-                            const uint32_t* d_order, const uint32_t* d_off, const uint8_t* d_disp, void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!q) return fail(c, ORL_E_INVALID, "null waiting queue");
-    if (n && (!d_tok || !d_mflags || !d_order || !d_off || !d_disp)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (n > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", n, (unsigned long long)c->s.max_batch);
-    if (n == 0) return ORL_OK;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    if (q->bound + n > q->capacity) {  // the bound may overstate: ask the device for the true length, on this path only
-        uint64_t len = 0;
-        ORL_HIP(c, hipMemcpyAsync(&len, q->waiting_n, sizeof(len), hipMemcpyDeviceToHost, st));
-        ORL_HIP(c, hipStreamSynchronize(st));
-        q->bound = len;
-        if (q->bound + n > q->capacity)
-            return fail(c, ORL_E_CAPACITY, "waiting queue: %llu records + a batch of %zu > capacity %llu",
-                        (unsigned long long)len, n, (unsigned long long)q->capacity);
-    }
-    int e = launch_waitq_append(*q, q->bound, d_tok, d_mflags, n, d_order, d_off, d_disp, st);
-    if (e) return hipfail(c, (hipError_t)e, "waiting queue append launch");
-    q->bound += n;
-    q->cur ^= 1u;
-    return ORL_OK;
-}
-
-int orl_complete_device(orl_ctx* c, orl_waitq* q, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
-                        const uint32_t* d_corder, const uint32_t* d_coff, orl_act_state* d_state, uint64_t* d_counts,
-                        void* stream) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!q) return fail(c, ORL_E_INVALID, "null waiting queue");
-    if (m && (!d_cact || !d_ctok || !d_corder || !d_coff || !d_state)) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (m > c->s.max_batch) return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", m, (unsigned long long)c->s.max_batch);
-    int e = launch_waitq_complete(*q, d_cact, d_ctok, m, d_coff, d_state, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "completion launch");
-    if (m) q->cur ^= 1u;
-    return ORL_OK;
-}
-
-// ---- the idle-activation collector (collect.hip) -------------------------------------------------------------
-int orl_collector_create(orl_ctx* c, int64_t quantum, int64_t now0, orl_collector** out) {
-    if (!c || !out) return ORL_E_INVALID;
-    *out = nullptr;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (quantum <= 0 || now0 <= 0) return fail(c, ORL_E_INVALID, "collector: quantum and now0 must be positive");
-    if (c->cfg.n_act > 0x80000000u) return fail(c, ORL_E_INVALID, "collector: n_act above 2^31");
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    const int64_t next = ((now0 - 1) / quantum + 1) * quantum;  // MakeTicketFromDateTime (ActivationCollector.cs:391-400)
-    if (int e = collector_alloc(out, c->cfg.n_act, c->s.max_batch, quantum, next))
-        return fail(c, ORL_E_NOMEM, "collector of %u activations: %s", c->cfg.n_act, hipGetErrorString((hipError_t)e));
-    return ORL_OK;
-}
-
-int orl_collector_destroy(orl_ctx* c, orl_collector* col) {
-    if (!c) return ORL_E_INVALID;
-    if (!col) return ORL_OK;
-    ORL_HIP(c, hipSetDevice(c->cfg.device));
-    collector_free(col);
-    return ORL_OK;
-}
-
-int orl_collector_view_get(orl_ctx* c, orl_collector* col, orl_collector_view* out) {
-    if (!c || !col || !out) return ORL_E_INVALID;
-    *out = orl_collector_view{col->ticket, col->became_idle, col->keep_alive_until, col->age_limit, col->cflags,
-                              col->out_act, col->out_n, col->quantum, col->next_ticket};
-    return ORL_OK;
-}
-
-// The checks every collector call shares; `count` is its m or n.
-static int collect_check(orl_ctx* c, orl_collector* col, size_t count, bool null_buffer, int64_t now) {
-    if (!c) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (!col) return fail(c, ORL_E_INVALID, "null collector");
-    if (now <= 0) return fail(c, ORL_E_INVALID, "collector: now must be positive");
-    if (count && null_buffer) return fail(c, ORL_E_INVALID, "null device buffer");
-    if (count > c->s.max_batch)
-        return fail(c, ORL_E_CAPACITY, "batch %zu > max_batch %llu", count, (unsigned long long)c->s.max_batch);
-    return ORL_OK;
-}
-
-int orl_collect_schedule_device(orl_ctx* c, orl_collector* col, const uint32_t* d_handles, size_t m, int64_t now,
-                                uint64_t* d_counts, void* stream) {
-    if (int rc = collect_check(c, col, m, !d_handles, now)) return rc;
-    int e = launch_collect_schedule(*col, d_handles, m, now, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector schedule launch");
-    return ORL_OK;
-}
-
-int orl_collect_cancel_device(orl_ctx* c, orl_collector* col, const uint32_t* d_handles, size_t m, uint64_t* d_counts,
-                              void* stream) {
-    if (int rc = collect_check(c, col, m, !d_handles, 1)) return rc;
-    int e = launch_collect_cancel(*col, d_handles, m, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector cancel launch");
-    return ORL_OK;
-}
-
-int orl_collect_touch_device(orl_ctx* c, orl_collector* col, const uint32_t* d_act, const uint8_t* d_disp, size_t n,
-                             const orl_act_state* d_state, const orl_admit_limits* limits, int64_t now, uint64_t* d_counts,
-                             void* stream) {
-    if (int rc = collect_check(c, col, n, !d_act || !d_disp || !d_state, now)) return rc;
-    if (!limits) return fail(c, ORL_E_INVALID, "null limits");
-    int e = launch_collect_touch(*col, d_act, d_disp, n, d_state, *limits, now, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector touch launch");
-    return ORL_OK;
-}
-
-int orl_collect_on_complete_device(orl_ctx* c, orl_collector* col, const uint32_t* d_cact, const uint32_t* d_ctok, size_t m,
-                                   const orl_act_state* d_state, int64_t now, uint64_t* d_counts, void* stream) {
-    if (int rc = collect_check(c, col, m, !d_cact || !d_ctok || !d_state, now)) return rc;
-    int e = launch_collect_on_complete(*col, d_cact, d_ctok, m, d_state, now, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector on-complete launch");
-    return ORL_OK;
-}
-
-int orl_collect_scan_stale_device(orl_ctx* c, orl_collector* col, orl_act_state* d_state, int64_t now, uint64_t* d_counts,
-                                  void* stream) {
-    if (int rc = collect_check(c, col, 1, !d_state, now)) return rc;
-    const int64_t old_next = col->next_ticket;
-    int64_t next = old_next;  // DequeueQuantum while nextTicket <= now (ActivationCollector.cs:186-210)
-    if (next <= now) next += ((now - next) / col->quantum + 1) * col->quantum;
-    int e = launch_collect_scan_stale(*col, d_state, now, old_next, next, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector ScanStale launch");
-    col->next_ticket = next;
-    return ORL_OK;
-}
-
-int orl_collect_scan_all_device(orl_ctx* c, orl_collector* col, orl_act_state* d_state, int64_t age_limit, int64_t now,
-                                uint64_t* d_counts, void* stream) {
-    if (int rc = collect_check(c, col, 1, !d_state, now)) return rc;
-    int e = launch_collect_scan_all(*col, d_state, age_limit, now, d_counts, stream ? stream : c->stream);
-    if (e) return hipfail(c, (hipError_t)e, "collector ScanAll launch");
     return ORL_OK;
 }
 
@@ -3246,7 +2043,7 @@ int orl_collect_scan_all_device(orl_ctx* c, orl_collector* col, orl_act_state* d
 int orl_device_alloc(orl_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return ORL_E_INVALID;
     *out = nullptr;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 1));
     if (e != hipSuccess) return fail(c, ORL_E_NOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
@@ -3263,35 +2060,35 @@ int orl_device_free(orl_ctx* c, void* p) {
 
 int orl_copy_to_device(orl_ctx* c, void* d_dst, const void* h_src, size_t bytes, void* stream) {
     if (!c || (bytes && (!d_dst || !h_src))) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (bytes) ORL_HIP(c, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, stream ? (hipStream_t)stream : c->stream));
+    if (int r = need_device(c)) return r;
+    if (bytes) ORL_HIP(c, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, stream_of(c, stream)));
     return ORL_OK;
 }
 
 int orl_copy_to_host(orl_ctx* c, void* h_dst, const void* d_src, size_t bytes, void* stream) {
     if (!c || (bytes && (!h_dst || !d_src))) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (bytes) ORL_HIP(c, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, stream ? (hipStream_t)stream : c->stream));
+    if (int r = need_device(c)) return r;
+    if (bytes) ORL_HIP(c, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, stream_of(c, stream)));
     return ORL_OK;
 }
 
 int orl_copy_on_device(orl_ctx* c, void* d_dst, const void* d_src, size_t bytes, void* stream) {
     if (!c || (bytes && (!d_dst || !d_src))) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
-    if (bytes) ORL_HIP(c, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, stream ? (hipStream_t)stream : c->stream));
+    if (int r = need_device(c)) return r;
+    if (bytes) ORL_HIP(c, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, stream_of(c, stream)));
     return ORL_OK;
 }
 
 int orl_stream_sync(orl_ctx* c, void* stream) {
     if (!c) return ORL_E_INVALID;
     if (!c->device_mode) return ORL_OK;
-    ORL_HIP(c, hipStreamSynchronize(stream ? (hipStream_t)stream : c->stream));
+    ORL_HIP(c, hipStreamSynchronize(stream_of(c, stream)));
     return ORL_OK;
 }
 
 int orl_host_register(orl_ctx* c, void* p, size_t bytes) {
     if (!c || !p || !bytes) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     ORL_HIP(c, hipSetDevice(c->cfg.device));
     ORL_HIP(c, hipHostRegister(p, bytes, hipHostRegisterDefault));
     return ORL_OK;
@@ -3306,7 +2103,7 @@ int orl_host_unregister(orl_ctx* c, void* p) {
 // ---- follower graph + host-array fan-out ------------------------------------------------------------
 int orl_csr_set(orl_ctx* c, const uint64_t* off, size_t n_nodes, const uint32_t* tgt, size_t n_edges) {
     if (!c || !off || (n_edges && !tgt)) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (off[0] != 0 || off[n_nodes] != n_edges) return fail(c, ORL_E_INVALID, "csr_off must start at 0 and end at n_edges");
     for (size_t i = 0; i < n_nodes; ++i)
         if (off[i + 1] < off[i]) return fail(c, ORL_E_INVALID, "csr_off not monotone at %zu", i);
@@ -3327,7 +2124,7 @@ int orl_fanout_batch(orl_ctx* c, const uint32_t* pubs, const uint8_t* pub_silo, 
                      uint32_t opts, uint64_t* pub_offsets, uint32_t* route, uint32_t* act, uint32_t* order, uint32_t* offsets,
                      size_t cap, uint64_t* n_out) {
     if (!c || !n_out || !pub_offsets) return ORL_E_INVALID;
-    if (!c->device_mode) return fail(c, ORL_E_STATE, "context was created without a device (device < 0)");
+    if (int r = need_device(c)) return r;
     if (!c->d_csr_off) return fail(c, ORL_E_STATE, "no follower graph (orl_csr_set)");
     const bool buckets = !(opts & ORL_OPT_NO_BUCKETS);
     if (n_pub && (!pubs || !pub_silo)) return fail(c, ORL_E_INVALID, "null publisher array");
@@ -3479,3 +2276,51 @@ int orl_timing_summary(const orl_ctx* cc, uint32_t* n_batches, float* route_ms, 
 }
 
 }  // extern "C"
+
+namespace orl {
+
+int ctx_route_received(orl_ctx* c, const void* d_in, int fmt, size_t n, uint32_t opts, uint32_t* d_route, uint32_t* d_act,
+                       const uint32_t* d_in_act, void* stream) {
+    return route_impl(c, d_in, fmt, n, opts | ORL_OPT_NO_BUCKETS, d_route, d_act, nullptr, nullptr, stream, d_in_act);
+}
+
+bool ctx_cache_on(orl_ctx* c) { return c && c->d_cache && c->hp.cache_on; }
+
+bool ctx_sw_on(const orl_ctx* c) { return c && c->sw_n != 0; }
+
+int ctx_keyext_prepare(orl_ctx* c) { return upload_keyext(c); }
+
+int ctx_route_keyext_received(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const orl_ext_ref* d_ext,
+                              const uint8_t* d_blob, uint64_t blob_bytes, uint32_t* d_route, uint32_t* d_act, void* stream) {
+    if (n == 0) return ORL_OK;
+    const uint32_t excl = (opts & ORL_OPT_EXCLUDE_IF_STOPPING) ? 1u : 0u;
+    int e = launch_keyext_route(c->d_params, d_in, n, d_ext, d_blob, blob_bytes, c->d_ext_table,
+                                c->ext_table.empty() ? 0 : c->ext_table.size() - 1, c->d_ext_blob, excl, d_route, d_act,
+                                stream_of(c, stream));
+    if (e) return hipfail(c, (hipError_t)e, "KeyExt route launch (node)");
+    return ORL_OK;
+}
+const uint32_t* ctx_stage4_err(const orl_ctx* c) { return c->s.s4_err; }
+
+// The node's hop-1 partition: any record width, with the status word (look-back failures included) for every width.
+int ctx_partition_padded(orl_ctx* c, const orl_msg_hdr* d_in, size_t n, uint32_t opts, const uint8_t* rank_of_silo,
+                         uint32_t nranks, uint32_t my_rank, size_t stride, void* d_out, int fmt, uint64_t* d_counts,
+                         uint32_t* d_status, void* stream, uint32_t* d_act_out, const KxLanes* kxl) {
+    if (!c || !rank_of_silo || !d_status) return ORL_E_INVALID;
+    if (fmt != 8 && fmt != 16 && fmt != 32) return fail(c, ORL_E_INVALID, "record width %d", fmt);
+    if (stride < n) return fail(c, ORL_E_INVALID, "stride %zu < batch %zu", stride, n);
+    if (fmt == 8 && c->hp.n_wire_types == 0) return fail(c, ORL_E_STATE, "8-byte records need the wire types (orl_wire_types_set)");
+    hipStream_t st = stream_of(c, stream);
+    int r = partition_prologue(c, d_in, n, rank_of_silo, nranks, my_rank, d_out, d_counts, st);
+    if (r) return r;
+    const bool cached = d_act_out && ctx_cache_on(c);
+    const SwView swv = sw_view(c);
+    int e = launch_partition_padded(c->d_params, d_in, n, opts, c->d_rank_of_silo, nranks, my_rank, stride, d_out, fmt, nullptr,
+                                    d_counts, d_status, c->s, st, cached ? c->d_cache : nullptr,
+                                    cached ? c->cache_slots - 1 : 0, cached ? d_act_out : nullptr, kxl, swv.n ? &swv : nullptr);
+    if (!e && cached) e = launch_cache_gen_advance(c->d_cache, c->cache_slots - 1, n, st);  // the sender's lookups' LRU stamps
+    if (e) return hipfail(c, (hipError_t)e, "node partition launch");
+    return ORL_OK;
+}
+
+}  // namespace orl

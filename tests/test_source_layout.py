@@ -1,5 +1,6 @@
 """The scan-shaped device code keeps its shared helpers in one place, and the case lists of the GPU tests
-reach the chunked regime of the one-workgroup tile scan for the constants that header holds.  Text files only: no GPU."""
+reach the chunked regime of the one-workgroup tile scan for the constants that header holds.  The host side is cut into
+units by subsystem behind one private context header.  Text files only: no GPU."""
 import os
 import re
 
@@ -44,10 +45,51 @@ def test_the_host_side_does_not_include_the_device_header():
     src = _sources()
     users = {f for f, text in src.items() if re.search(r'#include\s+"%s"' % re.escape(HEADER), text)}
     assert users == {"admit.hip", "waitq.hip", "collect.hip", "cache_evict.hip", "cache_adaptive.hip"}, users
-    for f in ("orl_api.cpp", "orl_node.cpp"):  # nor through a header of theirs
-        for inc in re.findall(r'#include\s+"([^"]+)"', src[f]):
-            assert os.path.basename(inc) not in users and inc != HEADER, (f, inc)
-            assert not re.search(r'#include\s+"%s"' % re.escape(HEADER), src.get(inc, "")), (f, inc)
+    host = [f for f in src if f.endswith(".cpp")]
+    assert "orl_node.cpp" in host and len(host) >= 6, host
+    for f in host:  # nor through a header of theirs, to any depth
+        seen, todo = set(), [f]
+        while todo:
+            for inc in re.findall(r'#include\s+"([^"]+)"', src[todo.pop()]):
+                assert os.path.basename(inc) not in users and inc != HEADER, (f, inc)
+                if inc in src and inc not in seen:
+                    seen.add(inc)
+                    todo.append(inc)
+
+
+# ---- the host side's layout ------------------------------------------------------------------------------
+CTX_HEADER = "orl_ctx.h"
+
+
+def test_the_context_struct_is_defined_once_in_its_header():
+    src = _sources()
+    where = {f: len(re.findall(r"\bstruct\s+orl_ctx\s*\{", text)) for f, text in src.items()}
+    assert {f: n for f, n in where.items() if n} == {CTX_HEADER: 1}, where
+
+
+def test_no_device_unit_includes_the_context_header():
+    src = _sources()
+    users = {f for f, text in src.items() if re.search(r'#include\s+"%s"' % re.escape(CTX_HEADER), text)}
+    assert users and all(f.endswith(".cpp") for f in users), users  # no .hip file, and no header a .hip file may include
+    assert "orl_node.cpp" not in users  # it keeps to the orl::ctx_* accessors
+
+
+def test_every_declared_entry_point_is_defined_in_exactly_one_unit():
+    header = open(os.path.join(ROOT, "include", "orleans_route.h")).read()
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", "", header, flags=re.S)
+    declared = sorted(set(re.findall(r"\b(orl_\w+)\s*\([^;{}]*\)\s*;", header)))
+    assert len(declared) > 100 and "orl_ctx_create" in declared and "orl_collect_scan_all_device" in declared, len(declared)
+    units = {f: text for f, text in _sources().items() if f.endswith((".cpp", ".hip"))}
+    for name in declared:
+        where = {f: _definitions(name, text) for f, text in units.items() if _definitions(name, text)}
+        assert len(where) == 1 and list(where.values()) == [1], (name, where)
+
+
+def test_no_file_closes_and_reopens_extern_c():
+    for f, text in _sources().items():
+        assert len(re.findall(r'extern\s+"C"\s*\{', text)) <= 1, f
+        if f.startswith("api_"):  # and a unit cut out of orl_api.cpp keeps its private helpers in one anonymous namespace
+            assert len(re.findall(r"^namespace\s*\{", text, flags=re.M)) <= 1, f
 
 
 def _constant(name):
